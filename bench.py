@@ -10,10 +10,14 @@ seed = r*blocks + b)), then (N > 1) the ranks exchange the per-block compressed 
   python bench.py --gpus N --steps K --warmup W          (no launcher: re-executes itself under torch.distributed.run, one rank per GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus 1 --steps 3 --warmup 1 --full   (everything below: other configurations, CPU baselines, checker, side legs)
+  python bench.py ... --dump-outputs DIR                 (the headline's outputs of its last timed step as DIR/*.npy, see dump_outputs)
 
 Rank 0 prints ONE JSON line.  Its top-level fields are BASELINE.json configs[1] (level 10, 65 536 x 256 KiB per
 GPU): `value` = whole-job input MB/s (MB = 10^6 B, as reference programs/bench.c:253-255) over the
-barrier-bracketed timed region of exactly --steps steps, max over ranks.  The same process then times the other
+barrier-bracketed timed region of exactly --steps steps, max over ranks; `ms_per_step` = that region / --steps.
+A plain run (no --full) does only that: set up, warm up, time the steps, dump the outputs when asked, print the line.
+With --full the same process then times the other
 BASELINE configs with the same --steps / --warmup and reports them under "configs": level 21 and level 30 at
 16 384 x 256 KiB (configs[2..3]) and configs[4] in BOTH readings: weak scaling — 6 656 x 4 MiB blocks PER GPU, two per
 table-holding wave — and strong scaling — 4 096 x 4 MiB blocks in the WHOLE job (SURVEY 8d read literally), 4 096 / N per GPU, the
@@ -54,9 +58,11 @@ combiner, tests/gpu_threads.c).  "concurrent_streams": 4 streams x 20 launches o
 (a launch smaller than the machine gets an arena of its own and runs beside the others).  "frames": the reference's own frame entry point LizardF_compressFrame on a 4 GiB host buffer.
 "end_to_end" is the PCIe-inclusive rate of the host-buffer entry (LizardGPU_compressBlocks_host_packed) on a 4 GiB sample
 of the headline workload, from pageable and from pinned memory — never `value`.
+"configs", "blocks_in_flight", "config1", "one_block_callers", "concurrent_streams", "end_to_end", "frames" and the CPU and
+checker fields (cpu_baseline*, speedup_*, blocks_checked*, checker) come with --full only.
 Only the cpu_baseline / verification legs touch oracle/ (as the checker); the timed region calls the product library.
 
-  python bench.py --level 21 --blocks 16384         one configuration only (profiling runs)
+  python bench.py --level 21 --blocks 16384         one configuration only (profiling runs; --full adds its CPU legs and checker)
 """
 import argparse
 import concurrent.futures
@@ -338,6 +344,35 @@ def verify_all_blocks(L, level, bs, nb, src, dst, sizes, stride, seed0, byte_blo
     return nb, n_bytes_checked, kind
 
 
+DUMP_SAMPLE_BYTES = 48 << 20      # float32 block contents in a --dump-outputs sample: the whole dump stays under 64 MB
+
+
+def dump_outputs(d, dst, sizes, stride, gathered):
+    """--dump-outputs DIR: what a caller of the timed path holds after its last step, so that two builds can be compared output
+    for output on the same inputs.  Rank 0's shard, as DIR/<name>.npy:
+      compressed_sizes    every block's compressed size (float64)
+      sample_blocks       the indices of a fixed, seeded sample of at most 32 blocks (float64)
+      sample_bytes        those blocks' compressed bytes, one row per block, -1 past the block's size (float32; a row keeps at most
+                          DUMP_SAMPLE_BYTES / 4 bytes of its block)
+      gathered_sizes, gathered_offsets   (N > 1) the whole job's sizes and output offsets from the size exchange (float64)"""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    sz = sizes.cpu().numpy().astype(np.int64)
+    nb = sz.size
+    width = min(stride, DUMP_SAMPLE_BYTES // 4)
+    k = max(1, min(32, nb, DUMP_SAMPLE_BYTES // (4 * width)))
+    idx = np.sort(np.random.default_rng(0).choice(nb, size=k, replace=False))
+    rows = dst.view(nb, stride)[torch.from_numpy(idx).to(dst.device), :width].cpu().numpy().astype(np.float32)
+    rows[np.arange(width)[None, :] >= sz[idx][:, None]] = -1.0
+    arrays = {"compressed_sizes": sz.astype(np.float64), "sample_blocks": idx.astype(np.float64), "sample_bytes": rows}
+    if gathered is not None:
+        arrays["gathered_sizes"] = gathered[0].cpu().numpy().astype(np.float64)
+        arrays["gathered_offsets"] = gathered[1].cpu().numpy().astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def launcher_argv(n, argv):
     """The command `python bench.py --gpus N ...` turns itself into when no launcher started it: the driver's own N > 1 form."""
     import socket
@@ -366,11 +401,20 @@ def main():
     ap.add_argument("--cpu-all-seconds", type=float, default=3.0, help="all-cores CPU baseline: seconds per level (0 = skip)")
     ap.add_argument("--cpu-all-cores-worker", nargs=4, type=float, default=None, metavar=("LEVEL", "BS", "NBLOCKS", "SECONDS"),
                     help="internal: run the all-cores CPU baseline in this (GPU-free) process and print its JSON")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the other configurations and run the CPU baselines, the checker and the side measurements; "
+                         "without it the run times the headline configuration alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step of the first configuration as DIR/<name>.npy")
     args = ap.parse_args()
     if args.cpu_all_cores_worker:
         lv, bs_, nbk, sec = args.cpu_all_cores_worker
         print(json.dumps(cpu_all_cores(int(lv), int(bs_), int(nbk), sec)))
         return
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:                                       # a plain run: the headline figure alone, no CPU legs, no checker
+        args.headline_only, args.no_cpu = True, True
 
     import numpy as np
     import torch
@@ -624,12 +668,14 @@ def main():
                 res["blocks_checked_bytes"] = n_by
                 res["checker"] = (f"{kind} (zero-state), {max(1, threads // world)} host threads per rank, every rank its own shard, "
                                   f"{round(time.perf_counter() - t0, 1)} s")
-        return res, (src, dst, sizes, stride)
+        return res, (dst, sizes, stride, gathered[0])
 
     with_cpu = not args.no_cpu
     results = []
-    for level, bs, nb, scaling in plan:
-        r, _ = run_config(level, bs, nb, with_cpu, scaling)
+    for i, (level, bs, nb, scaling) in enumerate(plan):
+        r, outs = run_config(level, bs, nb, with_cpu, scaling)
+        if i == 0 and args.dump_outputs and rank == 0:     # before the next configuration reuses the buffers
+            dump_outputs(args.dump_outputs, *outs)
         results.append(r)
 
     # SURVEY 8d gives configs[2..3] (levels 21 / 30) "the same inputs" as configs[1]; the line has carried them at 16 384 blocks per GPU

@@ -27,8 +27,8 @@ validate)
   ( timeout 600 tests/gpu_quick 512 > $O/gpu_quick.log 2>&1; echo "gpu_quick rc=$?" ) | tee $O/summary.txt
   ( timeout 1800 python -m pytest tests -m gpu -q > $O/pytest.log 2>&1; echo "pytest rc=$?" ) | tee -a $O/summary.txt; tail -4 $O/pytest.log | tee -a $O/summary.txt
   ( timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?" ) | tee -a $O/summary.txt
-  ( timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" ) | tee -a $O/summary.txt
-  ( cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/rocprof -o bench -- python $R/bench.py --no-cpu > $R/$O/bench_under_rocprof.json 2> $R/$O/rocprof.err; echo "rocprof rc=$?" ) | tee -a $O/summary.txt
+  ( timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" ) | tee -a $O/summary.txt
+  ( cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/rocprof -o bench -- python $R/bench.py --full --no-cpu > $R/$O/bench_under_rocprof.json 2> $R/$O/rocprof.err; echo "rocprof rc=$?" ) | tee -a $O/summary.txt
   find $O/rocprof -name "*kernel_stats.csv" -exec cp {} $O/rocprofv3_kernel_stats_bench.csv \;
   # the headline configuration alone: its kernel's mean duration must agree with the bench line's HIP events
   ( cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/rocprof_headline -o headline -- python $R/bench.py --headline-only --no-cpu > $R/$O/bench_headline_under_rocprof.json 2> $R/$O/rocprof_headline.err; echo "rocprof headline rc=$?" ) | tee -a $O/summary.txt
@@ -43,7 +43,7 @@ validate_slim)
   # counter passes of the four bench configurations, one gpu_bench line per remaining level
   ( timeout 1500 python -m pytest tests -m gpu -q > $O/pytest.log 2>&1; echo "pytest rc=$?" ) | tee $O/summary.txt; tail -4 $O/pytest.log | tee -a $O/summary.txt
   ( timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?" ) | tee -a $O/summary.txt
-  ( timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" ) | tee -a $O/summary.txt
+  ( timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" ) | tee -a $O/summary.txt
   ( cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/rocprof_headline -o headline -- python $R/bench.py --headline-only --no-cpu > $R/$O/bench_headline_under_rocprof.json 2> $R/$O/rocprof_headline.err; echo "rocprof headline rc=$?" ) | tee -a $O/summary.txt
   find $O/rocprof_headline -name "*kernel_stats.csv" -exec cp {} $O/rocprofv3_kernel_stats_bench_headline_only.csv \;
   find $O/rocprof_headline -name "*.csv" -size +1M -delete; find $O/rocprof_headline -name "*.db" -delete
@@ -52,14 +52,14 @@ validate_slim)
   for l in 11 31 12 32 33 13 14 15 16 17 35 37 20 40 22 41 42; do timeout 300 tests/gpu_bench $l 262144 16384 2 50 1024 2>&1 | tail -1 | tee -a $O/summary.txt; done ;;
 rocprof_all)
   # rocprofv3 kernel stats over EVERY BASELINE configuration of the bench line in one CSV
-  ( cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/rocprof -o bench -- python $R/bench.py --no-cpu --steps 3 --warmup 1 > $R/$O/bench_under_rocprof.json 2> $R/$O/rocprof.err; echo "rocprof rc=$?" ) | tee -a $O/summary.txt
+  ( cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/rocprof -o bench -- python $R/bench.py --full --no-cpu --steps 3 --warmup 1 > $R/$O/bench_under_rocprof.json 2> $R/$O/rocprof.err; echo "rocprof rc=$?" ) | tee -a $O/summary.txt
   find $O/rocprof -name "*kernel_stats.csv" -exec cp {} $O/rocprofv3_kernel_stats_bench_all_configs.csv \;
   find $O/rocprof -name "*.csv" -size +1M -delete; find $O/rocprof -name "*.db" -delete
   head -12 $O/rocprofv3_kernel_stats_bench_all_configs.csv ;;
 multirank)
   # the N > 1 bench path on the one device: the pytest form (self-launch and torchrun), then a larger self-launched line
   ( timeout 900 python -m pytest tests/test_bench_multirank.py -m gpu -q -x > $O/pytest_multirank.log 2>&1; echo "pytest multirank rc=$?" ) | tee -a $O/summary.txt; tail -5 $O/pytest_multirank.log
-  ( timeout 600 python bench.py --gpus 2 --transport host-bounce --steps 2 --warmup 1 --headline-only --strong --blocks 2048 --cpu-seconds 1 --cpu-all-seconds 0 > $O/bench_n2_selflaunch.json 2> $O/bench_n2.err; echo "bench n2 self-launch rc=$?" ) | tee -a $O/summary.txt
+  ( timeout 600 python bench.py --gpus 2 --full --transport host-bounce --steps 2 --warmup 1 --headline-only --strong --blocks 2048 --cpu-seconds 1 --cpu-all-seconds 0 > $O/bench_n2_selflaunch.json 2> $O/bench_n2.err; echo "bench n2 self-launch rc=$?" ) | tee -a $O/summary.txt
   cut -c1-700 $O/bench_n2_selflaunch.json; tail -5 $O/bench_n2.err ;;
 *) echo "unknown mode $MODE"; exit 2 ;;
 esac

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-configuration kernel durations out of ONE rocprofv3 --kernel-trace pass over bench.py.
+"""Per-configuration kernel durations out of ONE rocprofv3 --kernel-trace pass over bench.py --full.
 
   python scripts/kernel_trace_by_config.py <bench_kernel_trace.csv> <bench line .json> > profiles/rNN_rocprofv3_kernel_durations_by_config.csv
 

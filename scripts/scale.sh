@@ -12,7 +12,7 @@ NDEV=$(python -c "import torch; print(torch.cuda.device_count())")
 for N in $NS; do
   if [ "$N" -gt "$NDEV" ]; then echo "N=$N: only $NDEV device(s) visible — skipped (bench.py --transport host-bounce runs the code path on fewer devices, as a functional check)"; continue; fi
   # (python bench.py --gpus N launches its own ranks under torch.distributed.run since round 6 — the driver's form)
-  timeout 1800 python bench.py --gpus $N --steps $STEPS --warmup $WARMUP --no-cpu "$@" > $O/n$N.json 2> $O/n$N.err
+  timeout 1800 python bench.py --gpus $N --steps $STEPS --warmup $WARMUP --full --no-cpu "$@" > $O/n$N.json 2> $O/n$N.err
   echo "N=$N rc=$?"
 done
 python - "$O" $NS <<'PY'

@@ -59,10 +59,9 @@ def test_exports_cover_the_reference_library(lib):
       Lizard_XXH64_digest""".split()
     have = set(exported())
     assert not [n for n in need if n not in have]
-    if os.path.exists("/root/reference/lib/dll/liblizard.def"):
-        text = open("/root/reference/lib/dll/liblizard.def").read()
-        names = [l.strip() for l in text.split("EXPORTS")[1].splitlines() if l.strip()]
-        assert len(names) == 17 and not [n for n in names if n not in have]
+    # the EXPORTS section of lib/dll/liblizard.def, one name per line
+    names = open(os.path.join(util.GOLDEN_DIR, "liblizard_def_exports.txt")).read().split()
+    assert len(names) == 17 and not [n for n in names if n not in have]
 
 
 def test_bound_and_version_without_gpu(lib):
@@ -97,27 +96,22 @@ def test_no_gpu_means_loud_failure(lib):
     assert lib.LizardGPU_lastError() != b""
 
 
-REF = "/root/reference"
-
-
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "programs")), reason="reference checkout not present (GPU box)")
 def test_reference_cli_links_against_library(lib, tmp_path):
     """INTEGRATION.md section 1, literally: the reference's own CLI objects (bench, lizardio, lizardcli, datagen) linked
     against liblizard_amd.so and nothing else — block compressor, decoder, frame layer and xxhash are the product's.
-    Everything is compiled into a temporary directory from the sources where they lie.
+    The program is oracle/_ref/lizard_cli_amd, compiled by oracle/Makefile from the sources where they lie.
     Without a GPU the library must fail loudly and the frame layer then stores the blocks raw: the file still
     round-trips (through this library's frame decoder)."""
     import torch
-    srcs = ["programs/bench.c", "programs/lizardio.c", "programs/lizardcli.c", "programs/datagen.c"]   # and NO object of the reference's lib/
-    objs = []
-    for f in srcs:
-        o = str(tmp_path / (os.path.basename(f)[:-2] + ".o"))
-        subprocess.check_call(["gcc", "-O1", "-w", "-I", REF + "/lib", "-I", REF + "/lib/xxhash", "-I", REF + "/programs",
-                               "-DXXH_NAMESPACE=Lizard_", "-c", os.path.join(REF, f), "-o", o])
-        objs.append(o)
-    exe = str(tmp_path / "lizard_on_gpu_lib")
-    libdir = os.path.dirname(_lib.LIB_PATH)
-    subprocess.check_call(["gcc", "-o", exe] + objs + ["-L", libdir, "-llizard_amd", "-Wl,-rpath," + libdir])
+    exe = os.path.join(util.ROOT, "oracle", "_ref", "lizard_cli_amd")
+    if not os.path.exists(exe):
+        util.reference()                                                     # builds oracle/_ref when the checkout is present
+    if not os.path.exists(exe):
+        util.need_ref("oracle/_ref/lizard_cli_amd")
+    ldd = subprocess.check_output(["ldd", exe]).decode()
+    assert "liblizard_amd.so" in ldd and "liblizard_ref" not in ldd          # and NO object of the reference's lib/
+    undefined = subprocess.check_output(["nm", "-u", exe]).decode().split()
+    assert {"Lizard_compress", "Lizard_decompress_safe", "LizardF_compressBegin", "LizardF_decompress", "Lizard_XXH64"} <= set(undefined)
     out = subprocess.run([exe, "--version"], capture_output=True, text=True)
     assert "Lizard command line interface" in out.stdout + out.stderr
     if torch.cuda.is_available():

@@ -31,7 +31,7 @@ def test_bench_two_and_three_ranks_on_one_device(world, blocks, self_launch):
         extra = ["--transport", "host-bounce"]               # (a box with enough devices: still exercise the bounce transport here)
     else:
         extra = []
-    tail = ["--gpus", str(world), "--headline-only", "--strong", "--strong-blocks", "96",
+    tail = ["--gpus", str(world), "--full", "--headline-only", "--strong", "--strong-blocks", "96",
             "--blocks", str(blocks), "--steps", "2", "--warmup", "1", "--cpu-seconds", "1", "--cpu-all-seconds", "0"] + extra
     if self_launch:
         cmd = [sys.executable, os.path.join(util.ROOT, "bench.py")] + tail
