@@ -183,6 +183,7 @@ def test_gpu_decoder_matches_reference_decoder_and_host_forms(L):
 
 @pytest.mark.gpu
 def test_gpu_decoder_survives_damage(L):
+    import test_gpu_decoder_differential as D
     rnd = random.Random(13)
     data = util.datagen(200000, 0.5, 0.0, 5)
     for level in (10, 21, 30, 41):
@@ -201,6 +202,12 @@ def test_gpu_decoder_survives_damage(L):
         rc = L.LizardGPU_decompressBlocks_host(buf.ctypes.data, offs.ctypes.data, len(bad_blocks), out.ctypes.data, len(data), sz.ctypes.data)
         assert rc == 0
         assert all(s == 0xFFFFFFFF or s <= len(data) for s in sz)
+        # the same blocks in the guarded slot form (sentinel slots, canaries, tail guard, two read patterns), against the host decoder
+        items = [(b, len(data)) for b in bad_blocks]
+        res = D.guarded_decode(items, D._device_run)
+        assert [r for r, _ in res] == [int(s) for s in sz], level
+        assert all(o == out[i * len(data):i * len(data) + r].tobytes() for i, (r, o) in enumerate(res) if r != 0xFFFFFFFF), level
+        D.check_differential([(b, len(data), None, "L%d damaged" % level) for b in bad_blocks], res, twin=D.emul_decode)
 
 
 @pytest.mark.gpu
