@@ -8,10 +8,12 @@
  * extension.  Each entry cites the reference declaration it replaces.
  *   Part 1   block compression      lib/lizard_compress.h       on the GPU, no host path
  *   Part 1b  block decompression    lib/lizard_decompress.h     one block per call: on the calling thread (not the accelerated path)
- *   Part 1c  frames                 lib/lizard_frame.h          compression batched on the GPU; decompression on the host
+ *   Part 1c  frames                 lib/lizard_frame.h          compression batched on the GPU; LizardF_decompress on the host
+ *                                                               (a whole frame in one call on the GPU: LizardGPU_decompressFrame, Part 3b)
  *   Part 1d  XXH32 / XXH64          lib/xxhash/xxhash.h         (XXH_NAMESPACE=Lizard_, lib/Makefile:52)
  *   Part 2   batch extension (ours): many independent blocks per call, host- or device-resident, several GPUs, decompression
  *   Part 3   the strict frame twins of rounds 2-3 (LizardGPU_compressFrame ...)
+ *   Part 3b  whole-frame decompression on the GPU (LizardGPU_decompressFrame ...)
  *
  * Plain C, plain pointers and sizes; no HIP or torch types in any signature (a HIP stream is passed
  * as an opaque void*).
@@ -396,9 +398,11 @@ typedef LizardF_preferences_t LizardGPU_framePrefs_t;
 
 enum {                                       /* LizardF_errorCodes, lib/lizard_frame_static.h:57-67 */
     LIZARDGPU_FRAME_ERR_GENERIC = 1, LIZARDGPU_FRAME_ERR_maxBlockSize_invalid = 2, LIZARDGPU_FRAME_ERR_blockMode_invalid = 3,
-    LIZARDGPU_FRAME_ERR_compressionLevel_invalid = 5, LIZARDGPU_FRAME_ERR_allocation_failed = 9,
-    LIZARDGPU_FRAME_ERR_dstMaxSize_tooSmall = 11, LIZARDGPU_FRAME_ERR_frameType_unknown = 13,
-    LIZARDGPU_FRAME_ERR_frameSize_wrong = 14, LIZARDGPU_FRAME_ERR_maxCode = 19
+    LIZARDGPU_FRAME_ERR_compressionLevel_invalid = 5, LIZARDGPU_FRAME_ERR_headerVersion_wrong = 6,
+    LIZARDGPU_FRAME_ERR_blockChecksum_unsupported = 7, LIZARDGPU_FRAME_ERR_reservedFlag_set = 8, LIZARDGPU_FRAME_ERR_allocation_failed = 9,
+    LIZARDGPU_FRAME_ERR_dstMaxSize_tooSmall = 11, LIZARDGPU_FRAME_ERR_frameHeader_incomplete = 12, LIZARDGPU_FRAME_ERR_frameType_unknown = 13,
+    LIZARDGPU_FRAME_ERR_frameSize_wrong = 14, LIZARDGPU_FRAME_ERR_decompressionFailed = 16, LIZARDGPU_FRAME_ERR_headerChecksum_invalid = 17,
+    LIZARDGPU_FRAME_ERR_contentChecksum_invalid = 18, LIZARDGPU_FRAME_ERR_maxCode = 19
 };
 
 /* replaces LizardF_isError, lib/lizard_frame.h:59 / lizard_frame.c:179 */
@@ -422,6 +426,49 @@ size_t LizardGPU_compressBound(size_t srcSize, const LizardGPU_framePrefs_t* pre
 size_t LizardGPU_compressUpdate(LizardGPU_cctx_t* cctx, void* dstBuffer, size_t dstMaxSize, const void* srcBuffer, size_t srcSize);
 size_t LizardGPU_flush(LizardGPU_cctx_t* cctx, void* dstBuffer, size_t dstMaxSize);
 size_t LizardGPU_compressEnd(LizardGPU_cctx_t* cctx, void* dstBuffer, size_t dstMaxSize);
+
+/* =====================================================================================================
+ * Part 3b — whole frames decoded on the GPU.
+ *
+ * LizardF_decompress (Part 1c) stays what it is: streaming, any segmentation, one host thread.  These entries take ONE whole
+ * frame in host memory and decode every block that can be decoded on its own on the device, in batches: the host walks the
+ * header and the chain of block records, chunks of whole records go through pinned staging to lz_unframe_kernel (one wave per
+ * record: stored-raw records are copied, compressed ones decoded), up to three chunks in flight, and the calling thread finishes
+ * the chunks in order (copy to dst, content checksum).  A block of a LINKED frame that copies from before its own start is
+ * recognised exactly by the kernel and decoded on the host behind the bytes that are final by then; a linked frame in which most
+ * blocks do so (the reference's linked frames; never this library's, Part 1) is handed to the host decoder after its first chunk.
+ * The result is what LizardF_decompress produces for the same bytes; for damaged input the same refusals with the same codes for
+ * header, content-checksum, frame-size errors (a corrupt block: decompressionFailed in a linked frame, GENERIC in an independent one).
+ * Strict like Part 3: no device or a HIP failure is LIZARDGPU_FRAME_ERR_GENERIC (LizardGPU_lastError has the text), never a
+ * silent host decode.
+ * ===================================================================================================== */
+
+/* Decodes the ONE frame that starts at src.  Returns the bytes written to dst, or a code LizardGPU_frameIsError() recognises.
+ * *srcConsumedPtr (may be NULL) = bytes of src the frame occupied (0 on error): a caller walks concatenated frames by calling
+ * again.  A skippable frame decodes to 0 bytes.  dst too small for the frame: dstMaxSize_tooSmall; nothing outside
+ * dst[0..dstCapacity) is ever written.  A frame that ends before its end mark / checksum (LizardF_decompress would ask for more
+ * input): frameHeader_incomplete when src ends inside the header, GENERIC behind it. */
+size_t LizardGPU_decompressFrame(void* dst, size_t dstCapacity, const void* src, size_t srcSize, size_t* srcConsumedPtr);
+
+/* Upper bound of what the frame at src decodes to, without decoding: the sum over its block records of (stored raw ? record size
+ * : the frame's maximum block size), or the header's content size when it carries one that is smaller (for every frame
+ * LizardF_decompress accepts that is the exact size).  Error code as LizardGPU_decompressFrame for a header / record chain that
+ * is refused or ends early.  Pure host code. */
+size_t LizardGPU_decompressFrameBound(const void* src, size_t srcSize);
+
+/* The record table the decoder works from (pure host code, no device needed): for record i the byte offset in src of its payload
+ * (behind the LE32 word) and the word itself (bit 31 = stored raw).  Fills at most maxRecords entries (the arrays may be NULL),
+ * *nRecords = how many the frame has, *frameBytes = header + records + end mark + checksum; info (may be NULL) = the header's
+ * fields.  0 or -LIZARDGPU_FRAME_ERR_*. */
+int LizardGPU_frameIndex(const void* src, size_t srcSize, LizardGPU_frameInfo_t* info, uint64_t* payloadOffsets,
+                         uint32_t* recordWords, size_t maxRecords, size_t* nRecords, size_t* frameBytes);
+
+/* Since process start, selected device: [0] blocks decoded by the kernel, [1] raw records copied by the kernel, [2] blocks decoded
+ * again on the host because they reach into their history, [3] frames whose remainder was handed to the host decoder.
+ * 0 or -LIZARDGPU_ERR_*.  LizardGPU_frameDecodePackedChunks: chunks that had a short block in the middle and were packed on the
+ * device before the copy. */
+int LizardGPU_frameDecodeStats(unsigned long long out[4]);
+unsigned long long LizardGPU_frameDecodePackedChunks(void);
 
 #ifdef __cplusplus
 }

@@ -70,6 +70,23 @@ def lib():
     L.LizardGPU_gatherSizes_device.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p]
     L.LizardGPU_gatherSizes_device.restype = c.c_int
     L.LizardGPU_commDestroy.restype = c.c_int
+    L.LizardGPU_decompressBlocks_host.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p]
+    L.LizardGPU_decompressBlocks_host.restype = c.c_int
+    L.LizardGPU_decompressBlocks_device.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t,
+                                                    c.c_void_p, c.c_void_p]
+    L.LizardGPU_decompressBlocks_device.restype = c.c_int
+    L.LizardGPU_frameIsError.argtypes = [c.c_size_t]; L.LizardGPU_frameIsError.restype = c.c_uint
+    L.LizardF_getErrorName.argtypes = [c.c_size_t]; L.LizardF_getErrorName.restype = c.c_char_p
+    L.LizardGPU_compressFrameBound.argtypes = [c.c_size_t, c.c_void_p]; L.LizardGPU_compressFrameBound.restype = c.c_size_t
+    L.LizardGPU_compressFrame.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p]
+    L.LizardGPU_compressFrame.restype = c.c_size_t
+    L.LizardGPU_decompressFrame.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p]
+    L.LizardGPU_decompressFrame.restype = c.c_size_t
+    L.LizardGPU_decompressFrameBound.argtypes = [c.c_void_p, c.c_size_t]; L.LizardGPU_decompressFrameBound.restype = c.c_size_t
+    L.LizardGPU_frameIndex.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
+    L.LizardGPU_frameIndex.restype = c.c_int
+    L.LizardGPU_frameDecodeStats.argtypes = [c.c_void_p]; L.LizardGPU_frameDecodeStats.restype = c.c_int
+    L.LizardGPU_frameDecodePackedChunks.restype = c.c_ulonglong
     _lib = L
     return L
 
@@ -83,3 +100,13 @@ def check(rc, what):
         detail = lib().LizardGPU_lastError().decode(errors="replace")
         raise LizardAmdError(f"{what}: {_ERR.get(-rc, rc)} {detail}".strip())
     return rc
+
+
+def check_frame(code, what):
+    """A size_t result of the frame entries: the value, or LizardAmdError with the reference's error name."""
+    L = lib()
+    if L.LizardGPU_frameIsError(code):
+        name = L.LizardF_getErrorName(code).decode()
+        detail = L.LizardGPU_lastError().decode(errors="replace")
+        raise LizardAmdError(f"{what}: {name} {detail}".strip())
+    return code

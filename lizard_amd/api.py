@@ -81,3 +81,111 @@ def compress_blocks_device(src, block_size, level=LIZARD_MIN_CLEVEL, dst=None, s
                                            sizes.data_ptr(), level, ctypes.c_void_p(stream))
     _lib.check(rc, "LizardGPU_compressBlocks_device")
     return dst, sizes, stride
+
+
+def _host_array(data):
+    return np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+
+
+def decompress_blocks(blocks, max_block_size):
+    """Decode independent compressed blocks (what compress_blocks returns) in one batched GPU call; every block decodes to at
+    most max_block_size bytes. Returns a list of bytes; a corrupt block raises."""
+    L = _lib.lib()
+    blocks = [bytes(b) for b in blocks]
+    nb = len(blocks)
+    if nb == 0:
+        return []
+    offsets = np.zeros(nb + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(b) for b in blocks], dtype=np.uint64)
+    src = np.frombuffer(b"".join(blocks) or b"\0", dtype=np.uint8)
+    out = np.empty(nb * max_block_size, dtype=np.uint8)
+    sizes = np.zeros(nb, dtype=np.uint32)
+    rc = L.LizardGPU_decompressBlocks_host(src.ctypes.data, offsets.ctypes.data, nb, out.ctypes.data, max_block_size,
+                                           sizes.ctypes.data)
+    _lib.check(rc, "LizardGPU_decompressBlocks_host")
+    bad = [i for i in range(nb) if int(sizes[i]) == 0xFFFFFFFF]
+    if bad:
+        raise _lib.LizardAmdError(f"decompress_blocks: block {bad[0]} is corrupt or does not fit {max_block_size} bytes")
+    return [out[i * max_block_size:i * max_block_size + int(sizes[i])].tobytes() for i in range(nb)]
+
+
+def decompress_blocks_device(src, sizes, stride, block_size, dst=None, out_sizes=None):
+    """Device-resident batch in the layout compress_blocks_device returns: block i is sizes[i] bytes at src + i*stride.
+    Enqueues on torch's current stream and returns (dst, out_sizes): block i decoded at dst + i*block_size, out_sizes[i] its
+    size as int32 (-1: corrupt or larger than block_size)."""
+    import torch
+    L = _lib.lib()
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+    assert sizes.is_cuda and sizes.dtype == torch.int32 and sizes.is_contiguous()
+    nb = int(sizes.numel())
+    if dst is None:
+        dst = torch.empty(nb * block_size, dtype=torch.uint8, device=src.device)
+    if out_sizes is None:
+        out_sizes = torch.zeros(nb, dtype=torch.int32, device=src.device)
+    L.LizardGPU_setDevice(src.device.index or 0)
+    stream = torch.cuda.current_stream(src.device).cuda_stream
+    rc = L.LizardGPU_decompressBlocks_device(src.data_ptr(), stride, sizes.data_ptr(), nb, dst.data_ptr(), block_size,
+                                             out_sizes.data_ptr(), ctypes.c_void_p(stream))
+    _lib.check(rc, "LizardGPU_decompressBlocks_device")
+    return dst, out_sizes
+
+
+class _FrameInfo(ctypes.Structure):
+    _fields_ = [("blockSizeID", ctypes.c_uint), ("blockMode", ctypes.c_uint), ("contentChecksumFlag", ctypes.c_uint),
+                ("frameType", ctypes.c_uint), ("contentSize", ctypes.c_ulonglong), ("reserved", ctypes.c_uint * 2)]
+
+
+class _FramePrefs(ctypes.Structure):
+    _fields_ = [("frameInfo", _FrameInfo), ("compressionLevel", ctypes.c_int), ("autoFlush", ctypes.c_uint),
+                ("reserved", ctypes.c_uint * 4)]
+
+
+def compress_frame(data, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksum=False, content_size=False, independent=True):
+    """One Lizard frame (reference lib/lizard_frame.h) through LizardGPU_compressFrame: every block compressed in one batch
+    on the GPU. Linked frames (independent=False) larger than one block are refused by that strict entry."""
+    L = _lib.lib()
+    buf = _host_array(data)
+    p = _FramePrefs()
+    p.frameInfo.blockSizeID = block_size_id
+    p.frameInfo.blockMode = 1 if independent else 0
+    p.frameInfo.contentChecksumFlag = 1 if checksum else 0
+    p.frameInfo.contentSize = buf.size if content_size else 0
+    p.compressionLevel = level
+    cap = L.LizardGPU_compressFrameBound(buf.size, ctypes.byref(p))
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    n = _lib.check_frame(L.LizardGPU_compressFrame(out.ctypes.data, cap, buf.ctypes.data, buf.size, ctypes.byref(p)),
+                         "LizardGPU_compressFrame")
+    return out[:n].tobytes()
+
+
+def frame_info(data):
+    """Header fields and record table of the frame at the start of `data` (host code, no GPU): a dict with block_size_id,
+    independent, checksum, skippable, content_size, n_records, frame_bytes, bound."""
+    L = _lib.lib()
+    buf = _host_array(data)
+    info = _FrameInfo()
+    n, fb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    rc = L.LizardGPU_frameIndex(buf.ctypes.data, buf.size, ctypes.byref(info), None, None, 0, ctypes.byref(n), ctypes.byref(fb))
+    if rc:
+        _lib.check_frame((1 << 64) + rc, "LizardGPU_frameIndex")
+    return {"block_size_id": info.blockSizeID, "independent": bool(info.blockMode), "checksum": bool(info.contentChecksumFlag),
+            "skippable": bool(info.frameType), "content_size": info.contentSize, "n_records": n.value, "frame_bytes": fb.value,
+            "bound": L.LizardGPU_decompressFrameBound(buf.ctypes.data, buf.size)}
+
+
+def decompress_frame(data):
+    """Decode the frame(s) in `data` on the GPU (LizardGPU_decompressFrame); concatenated frames are decoded one after the
+    other and joined, skippable frames contribute nothing."""
+    L = _lib.lib()
+    buf = _host_array(data)
+    out, pos = [], 0
+    while pos < buf.size:
+        src = buf[pos:]
+        cap = _lib.check_frame(L.LizardGPU_decompressFrameBound(src.ctypes.data, src.size), "LizardGPU_decompressFrameBound")
+        dst = np.empty(max(cap, 1), dtype=np.uint8)
+        used = ctypes.c_size_t(0)
+        n = _lib.check_frame(L.LizardGPU_decompressFrame(dst.ctypes.data, cap, src.ctypes.data, src.size, ctypes.byref(used)),
+                             "LizardGPU_decompressFrame")
+        out.append(dst[:n].tobytes())
+        pos += used.value
+    return b"".join(out)

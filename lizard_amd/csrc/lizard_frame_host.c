@@ -453,13 +453,13 @@ size_t LizardF_freeDecompressionContext(LizardF_decompressionContext_t d)       
     return result;
 }
 
-/* Header of a frame at p[0..n), n = 7 or 15 as its FLG byte says (LizardF_decodeHeader, :756-857).  0 or an error code. */
-static size_t decode_header(LizardF_decompressionContext_t d, const uint8_t* p, size_t n)
+/* Header of a frame at p[0..n), n = 7 or 15 as its FLG byte says (LizardF_decodeHeader, :756-857): the checks and the fields, no
+ * state (shared by the streaming decoder below and by LizardGPU_frameIndex).  0 or an error code. */
+static size_t parse_header(const uint8_t* p, size_t n, LizardF_frameInfo_t* info, size_t* maxBlockSize)
 {
     const unsigned flg = p[4], bd = p[5];
     const unsigned version = (flg >> 6) & 3u, blockMode = (flg >> 5) & 1u, blockChecksum = (flg >> 4) & 1u, contentSizeFlag = (flg >> 3) & 1u,
                    contentChecksum = (flg >> 2) & 1u, bsid = (bd >> 4) & 7u;
-    size_t need;
     if (version != 1) return LZF_ERR(headerVersion_wrong);                                           /* :811-816 */
     if (blockChecksum) return LZF_ERR(blockChecksum_unsupported);
     if (flg & 3u) return LZF_ERR(reservedFlag_set);
@@ -467,16 +467,26 @@ static size_t decode_header(LizardF_decompressionContext_t d, const uint8_t* p, 
     if (bsid < 1) return LZF_ERR(maxBlockSize_invalid);
     if (bd & 0x0Fu) return LZF_ERR(reservedFlag_set);
     if ((uint8_t)(Lizard_XXH32(p + 4, n - 5, 0) >> 8) != p[n - 1]) return LZF_ERR(headerChecksum_invalid);   /* :819-820 */
-    memset(&d->info, 0, sizeof d->info);
-    d->info.blockMode = (LizardF_blockMode_t)blockMode;
-    d->info.contentChecksumFlag = (LizardF_contentChecksum_t)contentChecksum;
-    d->info.blockSizeID = (LizardF_blockSizeID_t)bsid;
-    d->maxBlockSize = block_size_of(bsid);
-    d->remaining = 0;
-    if (contentSizeFlag) {
-        d->info.contentSize = (unsigned long long)rd32le(p + 6) | ((unsigned long long)rd32le(p + 10) << 32);
-        d->remaining = d->info.contentSize;
-    }
+    memset(info, 0, sizeof *info);
+    info->blockMode = (LizardF_blockMode_t)blockMode;
+    info->contentChecksumFlag = (LizardF_contentChecksum_t)contentChecksum;
+    info->blockSizeID = (LizardF_blockSizeID_t)bsid;
+    *maxBlockSize = block_size_of(bsid);
+    if (contentSizeFlag) info->contentSize = (unsigned long long)rd32le(p + 6) | ((unsigned long long)rd32le(p + 10) << 32);
+    return 0;
+}
+
+static size_t decode_header(LizardF_decompressionContext_t d, const uint8_t* p, size_t n)
+{
+    LizardF_frameInfo_t info;
+    size_t need, maxBlockSize = 0;
+    const size_t e = parse_header(p, n, &info, &maxBlockSize);
+    unsigned blockMode, contentChecksum;
+    if (e) return e;
+    d->info = info;
+    d->maxBlockSize = maxBlockSize;
+    d->remaining = info.contentSize;
+    blockMode = (unsigned)info.blockMode; contentChecksum = (unsigned)info.contentChecksumFlag;
     if (contentChecksum) Lizard_XXH32_reset(&d->xxh, 0);
     /* decoded bytes: one block, plus — linked — the history behind it with room to slide only every 16 MiB */
     need = d->maxBlockSize + (blockMode == 0 ? 2 * LZF_DICT : 0);
@@ -727,4 +737,88 @@ size_t LizardF_getFrameInfo(LizardF_decompressionContext_t d, LizardF_frameInfo_
         *frameInfoPtr = d->info;
         return hint;
     }
+}
+
+/* ================================================= frame index (LizardGPU_decompressFrame works from it) ================================================= */
+
+/* One walk over the header and the chain of block records of the frame at src: the refusals of LizardF_decompress (parse_header,
+ * a record larger than the frame's block size), and two of its own for what a one-call decoder cannot leave to "call again with
+ * more input": frameHeader_incomplete when src ends inside the header (what LizardF_getFrameInfo answers), GENERIC when it ends
+ * anywhere behind it before the end mark and the checksum are in.  A skippable frame has no records. */
+int LizardGPU_frameIndex(const void* srcBuffer, size_t srcSize, LizardGPU_frameInfo_t* info, uint64_t* payloadOffsets, uint32_t* recordWords,
+                         size_t maxRecords, size_t* nRecords, size_t* frameBytes)
+{
+    const uint8_t* const p = (const uint8_t*)srcBuffer;
+    LizardF_frameInfo_t fi;
+    size_t hSize, pos, n = 0, maxBlockSize = 0, e;
+    uint32_t magic;
+    if (nRecords) *nRecords = 0;
+    if (frameBytes) *frameBytes = 0;
+    if (!p && srcSize) return -(int)LizardF_ERROR_GENERIC;
+    if (srcSize < 5) return -(int)LizardF_ERROR_frameHeader_incomplete;
+    magic = rd32le(p);
+    if ((magic & 0xFFFFFFF0u) == LZF_MAGIC_SKIPPABLE) {
+        if (srcSize < 8) return -(int)LizardF_ERROR_frameHeader_incomplete;
+        memset(&fi, 0, sizeof fi);
+        fi.frameType = LizardF_skippableFrame;
+        fi.contentSize = rd32le(p + 4);
+        if (info) *info = fi;
+        if (srcSize - 8 < (size_t)fi.contentSize) return -(int)LizardF_ERROR_GENERIC;
+        if (frameBytes) *frameBytes = 8 + (size_t)fi.contentSize;
+        return 0;
+    }
+    if (magic != LZF_MAGIC) return -(int)LizardF_ERROR_frameType_unknown;
+    hSize = ((p[4] >> 3) & 1u) ? LZF_MAX_HEADER : LZF_MIN_HEADER;
+    if (srcSize < hSize) return -(int)LizardF_ERROR_frameHeader_incomplete;
+    e = parse_header(p, hSize, &fi, &maxBlockSize);
+    if (e) return -(int)((size_t)0 - e);
+    if (info) *info = fi;
+    pos = hSize;
+    for (;;) {
+        uint32_t word;
+        size_t size;
+        if (srcSize - pos < 4) return -(int)LizardF_ERROR_GENERIC;
+        word = rd32le(p + pos);
+        size = word & 0x7FFFFFFFu;
+        pos += 4;
+        if (size == 0) break;                                                                         /* end mark */
+        if (size > maxBlockSize) return -(int)LizardF_ERROR_GENERIC;                                  /* :1076 */
+        if (srcSize - pos < size) return -(int)LizardF_ERROR_GENERIC;
+        if (n < maxRecords) {
+            if (payloadOffsets) payloadOffsets[n] = (uint64_t)pos;
+            if (recordWords) recordWords[n] = word;
+        }
+        n++;
+        pos += size;
+    }
+    if (fi.contentChecksumFlag) {
+        if (srcSize - pos < 4) return -(int)LizardF_ERROR_GENERIC;
+        pos += 4;
+    }
+    if (nRecords) *nRecords = n;
+    if (frameBytes) *frameBytes = pos;
+    return 0;
+}
+
+size_t lzgpu_frame_block_size(unsigned blockSizeID) { return block_size_of(blockSizeID); }
+
+size_t LizardGPU_decompressFrameBound(const void* srcBuffer, size_t srcSize)
+{
+    const uint8_t* const p = (const uint8_t*)srcBuffer;
+    LizardF_frameInfo_t fi;
+    size_t n = 0, i, frameBytes = 0, maxBlockSize, pos, sum = 0;
+    int rc = LizardGPU_frameIndex(srcBuffer, srcSize, &fi, NULL, NULL, 0, &n, &frameBytes);
+    if (rc) return (size_t)(long)rc;
+    if (fi.frameType == LizardF_skippableFrame) return 0;
+    maxBlockSize = block_size_of((unsigned)fi.blockSizeID);
+    pos = ((p[4] >> 3) & 1u) ? LZF_MAX_HEADER : LZF_MIN_HEADER;
+    for (i = 0; i < n; i++) {                                    /* (the chain has just been checked: no test repeated here) */
+        const uint32_t word = rd32le(p + pos);
+        const size_t size = word & 0x7FFFFFFFu;
+        sum += (word & 0x80000000u) ? size : maxBlockSize;
+        pos += 4 + size;
+    }
+    /* a header content size above what the records can hold is a frame LizardF_decompress ends with frameSize_wrong: the smaller
+     * value is still a bound for every frame it accepts, and keeps a damaged header from asking for an absurd buffer */
+    return fi.contentSize && fi.contentSize < (unsigned long long)sum ? (size_t)fi.contentSize : sum;
 }

@@ -17,6 +17,7 @@
 #include "lizard_gpu_shim.h"
 #include "lizard_gpu_ctx.h"
 #include "lz_kernels.h"   // LzBatch / LzUnBatch, residency knobs, the kernels
+#include "unframe_kernels.h"   // lz_unframe_kernel: the block records of a frame (LizardGPU_decompressFrame)
 
 namespace {
 
@@ -184,6 +185,8 @@ void ctx_release(Ctx& c)
         if (s.d_packed) (void)hipFree(s.d_packed);
         if (s.d_sizes) (void)hipFree(s.d_sizes);
         if (s.d_offsets) (void)hipFree(s.d_offsets);
+        if (s.d_aux) (void)hipFree(s.d_aux);
+        if (s.h_aux) (void)hipHostFree(s.h_aux);
         if (s.up) (void)hipEventDestroy(s.up);
         if (s.k0) (void)hipEventDestroy(s.k0);
         if (s.k1) (void)hipEventDestroy(s.k1);
@@ -510,6 +513,34 @@ int launch_decompress(Ctx& c, const void* d_src, const u64* d_offsets, size_t sr
     return 0;
 }
 
+// The records of one chunk of a frame (unframe_kernels.h).  Shares the context's own arena and counter with the compress launches
+// and lz_decompress_kernel, ordered by the same events.
+int launch_unframe(Ctx& c, const void* d_src, const u64* d_payloadOffsets, const u32* d_words, size_t nRecords, void* d_slots,
+                   size_t slotBytes, u32* d_outSizes, u32* d_packSizes, hipStream_t stream)
+{
+    if (!d_src || !d_payloadOffsets || !d_words || !d_slots || !d_outSizes || !d_packSizes || nRecords == 0 || nRecords > 0xFFFFFFFFu || slotBytes == 0) {
+        snprintf(t_err, sizeof t_err, "bad argument (null pointer or zero size)");
+        return -LIZARDGPU_ERR_ARG;
+    }
+    int rc = ctx_init(c);
+    if (rc) return rc;
+    LzUnframeBatch a;
+    a.src = (const u8*)d_src; a.payloadOffsets = d_payloadOffsets; a.words = d_words;
+    a.slots = (u8*)d_slots; a.slotBytes = slotBytes; a.outSizes = d_outSizes; a.packSizes = d_packSizes; a.nRecords = (u32)nRecords;
+    a.scratch = c.scratch; a.counter = c.counter;
+    u32 grid = (u32)((nRecords + LZ_WAVES_DEC - 1) / LZ_WAVES_DEC);
+    if (grid > (u32)c.cus) grid = (u32)c.cus;
+    if (c.timed) LZ_HIP(hipStreamWaitEvent(stream, c.ev1, 0));
+    LZ_HIP(hipMemsetAsync(c.counter, 0, 4, stream));
+    LZ_HIP(hipEventRecord(c.ev0, stream));
+    hipLaunchKernelGGL(lz_unframe_kernel, dim3(grid), dim3(64 * LZ_WAVES_DEC), 0, stream, a);
+    LZ_HIP(hipGetLastError());
+    LZ_HIP(hipEventRecord(c.ev1, stream));
+    c.timed = true; c.lastStream = stream; c.lastEv0 = c.ev0; c.lastEv1 = c.ev1;
+    c.hostKernelMs = -1.0f;
+    return 0;
+}
+
 }  // namespace
 
 #include "lizard_shard.h"   // single-process multi-device entry + RCCL size gather (uses Guard / launch above)
@@ -695,6 +726,11 @@ int   lzk_launch_decompress(LzCtx* c, const void* d_src, const uint64_t* d_offse
                             size_t nBlocks, void* d_dst, size_t dstStride, uint32_t* d_outSizes, hipStream_t stream)
 {
     return launch_decompress(*c, d_src, (const u64*)d_offsets, srcStride, d_srcSizes, nBlocks, d_dst, dstStride, d_outSizes, stream);
+}
+int   lzk_launch_unframe(LzCtx* c, const void* d_src, const uint64_t* d_payloadOffsets, const uint32_t* d_words, size_t nRecords, void* d_slots,
+                         size_t slotBytes, uint32_t* d_outSizes, uint32_t* d_packSizes, hipStream_t stream)
+{
+    return launch_unframe(*c, d_src, (const u64*)d_payloadOffsets, d_words, nRecords, d_slots, slotBytes, d_outSizes, d_packSizes, stream);
 }
 void  lzk_pack_launch(const void* d_in, const void* d_slots, size_t slot, const uint32_t* d_sizes, uint64_t* d_offsets, void* d_packed,
                       uint32_t nb, uint32_t blockSize, uint32_t lastBlockSize, int mode, hipStream_t stream)

@@ -24,6 +24,8 @@ typedef struct LzStage {
     uint8_t*  d_slots;  size_t d_slots_cap;
     uint8_t*  d_packed; size_t d_packed_cap;
     uint32_t* d_sizes;  uint64_t* d_offsets;  size_t d_meta_cap;
+    uint8_t*  d_aux;    size_t d_aux_cap;                   /* frame decoding: the chunk's record table and its results (small, like the meta arrays) */
+    uint8_t*  h_aux;    size_t h_aux_cap;                   /* pinned */
 } LzStage;
 
 /* The combiner of the one-block entry points (Lizard_compress & co, lizard_pipeline_host.c): callers that arrive while a batch
@@ -83,6 +85,7 @@ typedef struct LzCtx {
     int   lastSplit;            /* the last compress launch was the producer / consumer form (profile builds: where the records are) */
     int   laneOrderOk;          /* self-check at context creation: lanes of one DS atomic are served in lane order */
     float hostKernelMs;         /* sum over the chunks of the last host-buffer call (< 0: last call was a device call) */
+    unsigned long long unframeStats[5];   /* LizardGPU_frameDecodeStats [0..3], [4] = chunks packed on the device; since process start */
     LzStage stage[LZ_STAGES];
     LzCombine comb;
     pthread_mutex_t mu;
@@ -119,9 +122,19 @@ void  lzk_combiner_quiesce(LzCtx* c);
 void  lzk_combiner_resume(LzCtx* c);
 int   lzk_launch_decompress(LzCtx* c, const void* d_src, const uint64_t* d_offsets, size_t srcStride, const uint32_t* d_srcSizes,
                             size_t nBlocks, void* d_dst, size_t dstStride, uint32_t* d_outSizes, hipStream_t stream);
+/* the block records of one chunk of a frame (unframe_kernels.h): record i = word d_words[i], payload at d_src + d_payloadOffsets[i],
+ * decoded into slot i * slotBytes; d_outSizes[i] = size / 0xFFFFFFFE (needs history) / 0xFFFFFFFF, d_packSizes[i] = valid bytes of the slot */
+int   lzk_launch_unframe(LzCtx* c, const void* d_src, const uint64_t* d_payloadOffsets, const uint32_t* d_words, size_t nRecords, void* d_slots,
+                         size_t slotBytes, uint32_t* d_outSizes, uint32_t* d_packSizes, hipStream_t stream);
 /* exclusive scan of the record sizes + compaction of the valid bytes into d_packed (lz_pack.h); mode: LZK_PACK_* */
 void  lzk_pack_launch(const void* d_in, const void* d_slots, size_t slot, const uint32_t* d_sizes, uint64_t* d_offsets, void* d_packed,
                       uint32_t nb, uint32_t blockSize, uint32_t lastBlockSize, int mode, hipStream_t stream);
+/* lizard_pipeline_host.c: its staging helpers, shared with lizard_unframe_host.c */
+int    lzp_ensure_dev(LzCtx* c, void** p, size_t* cap, size_t need);
+int    lzp_ensure_pinned(void** p, size_t* cap, size_t need);
+void   lzp_par_memcpy(void* dst, const void* src, size_t n);
+int    lzp_is_pinned_host(const void* p);
+size_t lzp_chunk_bytes(const LzCtx* ctx);
 #define LZK_PACK_PAYLOAD 0
 #define LZK_PACK_FRAME   1
 #ifdef __cplusplus

@@ -767,3 +767,10 @@ int LizardGPU_decompress_safe(const char* source, char* dest, int compressedSize
     free(tmp);
     return (int)out;
 }
+
+/* the staging helpers above, for the frame decoder's pipeline (lizard_unframe_host.c) */
+int    lzp_ensure_dev(LzCtx* c, void** p, size_t* cap, size_t need) { return ensure_dev(c, p, cap, need); }
+int    lzp_ensure_pinned(void** p, size_t* cap, size_t need) { return ensure_pinned(p, cap, need); }
+void   lzp_par_memcpy(void* dst, const void* src, size_t n) { par_memcpy(dst, src, n); }
+int    lzp_is_pinned_host(const void* p) { return is_pinned_host(p); }
+size_t lzp_chunk_bytes(const LzCtx* ctx) { return chunk_bytes(ctx); }

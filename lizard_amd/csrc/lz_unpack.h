@@ -20,6 +20,7 @@
 #include "lz_wave.h"
 
 #define LZD_ERR 0xFFFFFFFFu
+#define LZD_NEED_HISTORY 0xFFFFFFFEu      // lz_decompress_block_hist only: a match reaches in front of the block's own output
 
 // LDS workspace of one decoding wave (u32 words)
 #define LZD_WS_DT     0u          // u16[4096]  huff0 decoding table: symbol | nbBits << 8         (8 KiB)
@@ -362,9 +363,13 @@ LZ_DEV void lzd_copy_match(u8* out, u32 op, u32 off, u32 n)
 }
 
 // ---- one block.  in[0..inSize) -> out[0..outCap).  stage: 4 x (128 KiB + 32) bytes of global scratch; ws: LZD_WS_WORDS of LDS.
-// Returns the decoded size (uniform) or LZD_ERR. ----
+// Returns the decoded size (uniform) or LZD_ERR.  HIST (the frame decoder, unframe_kernels.h): a block of a linked frame may copy
+// from before its own start; that block is not corrupt, it needs bytes this wave does not have, and is reported as
+// LZD_NEED_HISTORY — exactly for a match with off != 0 && off > op, the one place where history changes what a decoder does
+// (every reference inside the block decodes the same with or without it).  Everything else stays LZD_ERR. ----
 #define LZD_STAGE_BYTES (131072u + 32u)
-LZ_DEV u32 lz_decompress_block(const u8* in, u32 inSize, u8* out, u32 outCap, u8* stage, u32* ws)
+template <bool HIST>
+LZ_DEV u32 lz_decompress_block_body(const u8* in, u32 inSize, u8* out, u32 outCap, u8* stage, u32* ws)
 {
     const u32 lane = lz_lane();
     if (inSize < 1u) return 0;                                   // lizard_decompress.c:139
@@ -397,6 +402,7 @@ LZ_DEV u32 lz_decompress_block(const u8* in, u32 inSize, u8* out, u32 outCap, u8
         if (!lzd_read_stream(res & 2u, in, pos, inSize, stage + 1u * LZD_STAGE_BYTES, LZD_STAGE_BYTES, pf, nf, ws)) return LZD_ERR;
         if (!lzd_read_stream(res & 1u, in, pos, inSize, stage, LZD_STAGE_BYTES, pl, nl, ws)) return LZD_ERR;
         // ---- sequences ----
+        const u32 opSub = op;                                    // where this sub-block's output starts
         u32 lp = 0, o16 = 0, o24 = 0;                            // uniform cursors into literals / off16 / off24
         u32 last_off = 0;                                        // LIZv1 repeat offset; the encoder never opens a sub-block with a repeat
         LzdWin win; win.wv = 0; win.base = 0; win.valid = false; // (a token without an escape — most LIZv1 tokens — never touches it)
@@ -472,7 +478,9 @@ LZ_DEV u32 lz_decompress_block(const u8* in, u32 inSize, u8* out, u32 outCap, u8
                     off = last_off;
                 }
                 if (ml) {                                        // (LIZv1: a literal-only token has match length 0)
-                    if (off == 0u || off > op || ml > outCap - op) return LZD_ERR;   // lz4.h:93 / liz.h:165
+                    if (off == 0u) return LZD_ERR;               // lz4.h:93 / liz.h:165
+                    if (off > op) return HIST ? LZD_NEED_HISTORY : LZD_ERR;
+                    if (ml > outCap - op) return LZD_ERR;
                     lz_wave_sync();                              // the bytes the match copies from have been written by other lanes
                     lzd_copy_match(out, op, off, ml);
                     op += ml;
@@ -484,6 +492,18 @@ LZ_DEV u32 lz_decompress_block(const u8* in, u32 inSize, u8* out, u32 outCap, u8
         lzd_copy(out + op, pl + lp, nl - lp);
         op += nl - lp;
         lz_wave_sync();                                          // staging areas are reused by the next sub-block
+        // lizard_decompress.c:248: a compressed sub-block that decodes to nothing ends the block with result 0, whatever came
+        // before it.  No compressor writes one; the frame decoder follows the host decoder there so that a damaged frame fails
+        // in the same place for both (the block entry keeps its own, stricter course: it goes on with the next sub-block).
+        if (HIST && op == opSub) return 0;
     }
     return op;
+}
+LZ_DEV u32 lz_decompress_block(const u8* in, u32 inSize, u8* out, u32 outCap, u8* stage, u32* ws)
+{
+    return lz_decompress_block_body<false>(in, inSize, out, outCap, stage, ws);
+}
+LZ_DEV u32 lz_decompress_block_hist(const u8* in, u32 inSize, u8* out, u32 outCap, u8* stage, u32* ws)
+{
+    return lz_decompress_block_body<true>(in, inSize, out, outCap, stage, ws);
 }
