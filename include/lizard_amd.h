@@ -332,8 +332,8 @@ float LizardGPU_lastKernelMs(void);
 /* Number of resident waves (= blocks compressed concurrently) the launcher uses on this device. */
 int LizardGPU_residentWaves(void);
 
-/* Launches on different streams.  A launch needs a scratch arena (2.6 GiB), a block counter and — levels 11/31, 21/41, 22/42 —
- * per-wave tables to itself.  Launches that fill the machine, the hashChain levels and decompression share the context's own and
+/* Launches on different streams.  A launch needs a scratch arena (2.6 GiB), a block counter and — levels 11/31, 20/40, 21/41,
+ * 22/42 — per-wave tables to itself.  Launches that fill the machine, the hashChain levels and decompression share the context's own and
  * run one after the other (the second waits on the device for the first); a compress launch SMALLER than the machine that arrives
  * on another stream while that arena is busy gets one of up to three more, allocated on first need, and runs beside it on the CUs
  * it leaves free.  LIZARDGPU_ARENAS=1..4 caps the total (default 4; 1 = every launch waits for the previous one).
@@ -342,7 +342,7 @@ int LizardGPU_arenasInUse(void);
 
 /* Device memory.  A context (one per device) keeps a scratch arena (one slot per resident wave: 2.7 GB on a 256-CU device), and
  * allocates on first use: up to three more arenas for small launches on concurrent streams (released again after 64 launches that
- * did not need them), per-wave tables (levels 21/41: 256 MiB; 11/31/22/42: 4 GiB), hashChain work areas (levels 12-17 / 32-38: up
+ * did not need them), per-wave tables (levels 20/40/21/41: 256 MiB; 11/31/22/42: 4 GiB), hashChain work areas (levels 12-17 / 32-38: up
  * to half of the free memory, at most 128 GiB), and the staging of the host-buffer entries (three chunks of 256 MiB in flight).
  * LizardGPU_setMemoryBudget(bytes) bounds the sum per device (0 = no bound, the default): tables and work areas then get fewer
  * slots than there are resident waves (fewer blocks in flight: slower, same bytes), what another level left behind is given up

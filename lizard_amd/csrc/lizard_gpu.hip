@@ -2,7 +2,8 @@
 //
 // The kernels live in lz_kernels.h (one wavefront per Lizard API block, a persistent grid of one workgroup per CU).
 // This file is the HIP side of the host layer: one context PER DEVICE (arenas, tables, streams), a per-thread device selection
-// and error text, the launcher, the device-buffer entry points, the shim the host C files call (lizard_gpu_ctx.h:
+// and error text, the launcher (kLevels: what a level runs; launch(): validate, look the row up, pick_arena, the row's tables, grid,
+// enqueue_on), the device-buffer entry points, the shim the host C files call (lizard_gpu_ctx.h:
 // lizard_pipeline_host.c holds the pipelined host-buffer path, in C), and the single-process multi-device entry with an RCCL
 // all-gather of the per-block sizes (lizard_shard.h).
 #include <hip/hip_runtime.h>
@@ -118,31 +119,49 @@ struct Guard : LzGuard {
     ~Guard() { guard_release(*this); }
 };
 
-static int ctx_init_body(Ctx& c);
-void ctx_release(Ctx& c);
-int ctx_init(Ctx& c)
+// An arena (lizard_gpu_ctx.h, LzArena): scratch, block counter and the events around its last launch; its per-wave tables come
+// on first use (alloc_table_slots).  A failed arena_create leaves what it got for arena_destroy.
+enum TableClass { kWide18 = 0, kPf64k = 1, kHashChain, kNoTables };   // the first LZ_ARENA_TABLES index LzArena::tables; the hashChain work areas are the context's
+const size_t kTableStride[LZ_ARENA_TABLES] = { LZ_TABWIDE_BYTES(18), LZ_PF_SLOT_BYTES };
+const char* const kTableWhat[LZ_ARENA_TABLES] = { "tables of levels 11/31/22/42", "tables of levels 20/40/21/41" };
+
+int arena_create(Ctx& c, LzArena& x)
 {
-    if (c.ready) return 0;
-    const int rc = ctx_init_body(c);
-    if (rc) {                                                   // a failure half way: what was taken goes back (and is no longer counted against the budget)
-        c.ready = 1; ctx_release(c);
-        (void)hipGetLastError();
-    }
-    return rc;
+    memset(&x, 0, sizeof x);
+    const int rc = dev_alloc(c, (void**)&x.scratch, (size_t)c.cus * kScratchBytes, "scratch arena");   // one slot per resident wave (one workgroup per CU)
+    if (rc) return rc;
+    LZ_HIP(hipMalloc((void**)&x.counter, 64));
+    LZ_HIP(hipEventCreate(&x.ev0));
+    LZ_HIP(hipEventCreate(&x.ev1));
+    return 0;
 }
-static int ctx_init_body(Ctx& c)
+void arena_free_tables(Ctx& c, LzArena& x, int keep)
+{
+    for (int k = 0; k < LZ_ARENA_TABLES; k++)
+        if (k != keep) { dev_free(c, x.tables[k], x.tableSlots[k] * kTableStride[k]); x.tables[k] = nullptr; x.tableSlots[k] = 0; }
+}
+void arena_destroy(Ctx& c, LzArena& x)                          // (its launches have finished: caller's business)
+{
+    if (c.lastEv0 == x.ev0 || c.lastEv1 == x.ev1) { c.lastEv0 = c.arena[0].ev0; c.lastEv1 = c.arena[0].ev1; }      // (LizardGPU_lastKernelMs must not look at destroyed events)
+    dev_free(c, x.scratch, (size_t)c.cus * kScratchBytes);
+    if (x.counter) (void)hipFree(x.counter);
+    arena_free_tables(c, x, kNoTables);
+    if (x.ev0) (void)hipEventDestroy(x.ev0);
+    if (x.ev1) (void)hipEventDestroy(x.ev1);
+    memset(&x, 0, sizeof x);
+}
+
+int ctx_init_body(Ctx& c)
 {
     hipDeviceProp_t prop;
     LZ_HIP(hipGetDeviceProperties(&prop, c.device));
     c.cus = prop.multiProcessorCount;
-    { const int rc_ = dev_alloc(c, (void**)&c.scratch, (size_t)c.cus * kScratchBytes, "scratch arena"); if (rc_) return rc_; }   // one slot per resident wave (one workgroup per CU)
+    LzArena& own = c.arena[0];
+    { const int rc_ = arena_create(c, own); if (rc_) return rc_; }
 #ifdef LZ_PROFILE
-    LZ_HIP(hipMemset(c.scratch, 0, (size_t)c.cus * LZ_MAX_WAVES * LZ_SCRATCH_BYTES));
+    LZ_HIP(hipMemset(own.scratch, 0, (size_t)c.cus * kScratchBytes));
 #endif
-    LZ_HIP(hipMalloc((void**)&c.counter, 64));
-    LZ_HIP(hipEventCreate(&c.ev0));
-    LZ_HIP(hipEventCreate(&c.ev1));
-    c.nExtra = 0; c.nextExtra = 0; c.maxArenas = LZ_ARENAS_MAX; c.lastStream = nullptr; c.lastEv0 = c.ev0; c.lastEv1 = c.ev1;
+    c.nArenas = 1; c.nextExtra = 0; c.maxArenas = LZ_ARENAS_MAX; c.lastEv0 = own.ev0; c.lastEv1 = own.ev1;
     if (const char* e = getenv("LIZARDGPU_ARENAS")) { const int n = atoi(e); if (n >= 1 && n <= LZ_ARENAS_MAX) c.maxArenas = n; }
     for (Stage& s : c.stage) {
         LZ_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
@@ -155,11 +174,11 @@ static int ctx_init_body(Ctx& c)
     // fails it keeps working for the other levels; the dependent ones are refused, loudly (launch()).
     // LIZARDGPU_FORCE_LANE_ORDER_FAILURE=1 takes the failure branch on a healthy device (tests).
     {
-        LZ_HIP(hipMemset(c.counter, 0, 4));
-        hipLaunchKernelGGL(lz_selfcheck_lane_order_kernel, dim3(16), dim3(64), 0, 0, c.counter, 256u);
+        LZ_HIP(hipMemset(own.counter, 0, 4));
+        hipLaunchKernelGGL(lz_selfcheck_lane_order_kernel, dim3(16), dim3(64), 0, 0, own.counter, 256u);
         LZ_HIP(hipGetLastError());
         u32 bad = 0;
-        LZ_HIP(hipMemcpy(&bad, c.counter, 4, hipMemcpyDeviceToHost));
+        LZ_HIP(hipMemcpy(&bad, own.counter, 4, hipMemcpyDeviceToHost));
         const char* force = getenv("LIZARDGPU_FORCE_LANE_ORDER_FAILURE");
         c.laneOrderOk = bad == 0 && !(force && force[0] == '1');
         if (!c.laneOrderOk)
@@ -168,6 +187,12 @@ static int ctx_init_body(Ctx& c)
     }
     c.ready = true;
     return 0;
+}
+
+void free_hc_slots(Ctx& c)
+{
+    dev_free(c, c.hcSlots, c.hcNSlots * c.hcSlotBytes);
+    c.hcSlots = nullptr; c.hcNSlots = 0; c.hcMaxBlock = 0; c.hcHasBest = 0; c.hcSlotBytes = 0;
 }
 
 void ctx_release(Ctx& c)
@@ -196,67 +221,50 @@ void ctx_release(Ctx& c)
         memset(&s, 0, sizeof s);
     }
     lzk_combiner_free(&c);
-    for (int i = 0; i < c.nExtra; i++) {
-        LzArena& x = c.extra[i];
-        if (x.scratch) (void)hipFree(x.scratch);
-        if (x.counter) (void)hipFree(x.counter);
-        if (x.tables) (void)hipFree(x.tables);
-        if (x.pfTables) (void)hipFree(x.pfTables);
-        if (x.ev0) (void)hipEventDestroy(x.ev0);
-        if (x.ev1) (void)hipEventDestroy(x.ev1);
-        memset(&x, 0, sizeof x);
+    for (LzArena& x : c.arena) arena_destroy(c, x);             // (every slot: one that was never made, or made half, holds nulls)
+    free_hc_slots(c);
+    c.nArenas = 0; c.nextExtra = 0; c.lastEv0 = c.lastEv1 = nullptr; c.laneOrderOk = 1; c.ready = 0;
+    c.devBytes = 0; c.idleLaunches = 0;
+}
+
+int ctx_init(Ctx& c)
+{
+    if (c.ready) return 0;
+    const int rc = ctx_init_body(c);
+    if (rc) {                                                   // a failure half way: what was taken goes back (and is no longer counted against the budget)
+        c.ready = 1; ctx_release(c);
+        (void)hipGetLastError();
     }
-    c.nExtra = 0;
-    if (c.tables) (void)hipFree(c.tables);
-    if (c.pfTables) (void)hipFree(c.pfTables);
-    if (c.hcSlots) (void)hipFree(c.hcSlots);
-    c.hcNSlots = 0; c.hcHasBest = 0; c.hcSlotBytes = 0;
-    if (c.scratch) (void)hipFree(c.scratch);
-    if (c.counter) (void)hipFree(c.counter);
-    if (c.ev0) (void)hipEventDestroy(c.ev0);
-    if (c.ev1) (void)hipEventDestroy(c.ev1);
-    c.tables = c.pfTables = c.hcSlots = c.scratch = nullptr; c.counter = nullptr; c.hcMaxBlock = 0;
-    c.ev0 = c.ev1 = c.lastEv0 = c.lastEv1 = nullptr; c.timed = 0; c.laneOrderOk = 1; c.ready = 0;
-    c.tablesSlots = c.pfSlots = 0; c.devBytes = 0; c.idleLaunches = 0;
+    return rc;
 }
 
 void free_extra_arenas(Ctx& c)                                   // (their launches have finished: caller's business)
 {
-    for (int i = 0; i < c.nExtra; i++) {
-        LzArena& x = c.extra[i];
-        if (c.lastEv0 == x.ev0 || c.lastEv1 == x.ev1) { c.lastEv0 = c.ev0; c.lastEv1 = c.ev1; }      // (LizardGPU_lastKernelMs must not look at destroyed events)
-        dev_free(c, x.scratch, (size_t)c.cus * kScratchBytes);
-        if (x.counter) (void)hipFree(x.counter);
-        dev_free(c, x.tables, x.tablesSlots * LZ_TABWIDE_BYTES(18));
-        dev_free(c, x.pfTables, x.pfSlots * LZ_PF_SLOT_BYTES);
-        if (x.ev0) (void)hipEventDestroy(x.ev0);
-        if (x.ev1) (void)hipEventDestroy(x.ev1);
-        memset(&x, 0, sizeof x);
-    }
-    c.nExtra = 0; c.nextExtra = 0;
+    for (int i = 1; i < c.nArenas; i++) arena_destroy(c, c.arena[i]);
+    c.nArenas = 1; c.nextExtra = 0;
 }
-// Everything but the context's own arena: extra arenas, per-wave tables, hashChain work areas (`keep`: 0 none, 1 tables, 2 pfTables,
-// 3 hcSlots).  The device is idle afterwards (synchronised first: other launches may still be using what is freed).
-void free_tables_except(Ctx& c, int keep)
+// Everything but the context's own scratch arena: extra arenas, per-wave tables, hashChain work areas, except the tables of class
+// `keep` (kNoTables: none).  The device is idle afterwards (synchronised first: other launches may still be using what is freed).
+void free_tables_except(Ctx& c, TableClass keep)
 {
     (void)hipDeviceSynchronize();
     free_extra_arenas(c);
-    if (keep != 1 && c.tables) { dev_free(c, c.tables, c.tablesSlots * LZ_TABWIDE_BYTES(18)); c.tables = nullptr; c.tablesSlots = 0; }
-    if (keep != 2 && c.pfTables) { dev_free(c, c.pfTables, c.pfSlots * LZ_PF_SLOT_BYTES); c.pfTables = nullptr; c.pfSlots = 0; }
-    if (keep != 3 && c.hcSlots) { dev_free(c, c.hcSlots, c.hcNSlots * c.hcSlotBytes); c.hcSlots = nullptr; c.hcNSlots = 0; c.hcMaxBlock = 0; c.hcHasBest = 0; c.hcSlotBytes = 0; }
+    arena_free_tables(c, c.arena[0], keep);
+    if (keep != kHashChain && c.hcSlots) free_hc_slots(c);
 }
-// Per-wave table slots of `stride` bytes under the budget: as many as resident waves if they fit — after giving up what other
-// levels left behind, if need be — else as many as fit (the waves without one leave, lz_wave_main); none: out of memory.
-int alloc_table_slots(Ctx& c, uint8_t** at, size_t* slotsAt, size_t stride, int kind, bool ownArena, const char* what)
+// Per-wave table slots of class k for arena x under the budget: as many as resident waves if they fit — the context's own arena
+// after giving up what other levels left behind, if need be — else as many as fit (the waves without one leave, lz_wave_main);
+// none: out of memory.
+int alloc_table_slots(Ctx& c, LzArena& x, TableClass k)
 {
-    const size_t want = (size_t)c.cus * LZ_MAX_WAVES;
-    if (want * stride > budget_room(c) && ownArena) free_tables_except(c, kind);
+    const size_t want = (size_t)c.cus * LZ_MAX_WAVES, stride = kTableStride[k];
+    if (want * stride > budget_room(c) && &x == &c.arena[0]) free_tables_except(c, k);
     size_t slots = budget_room(c) / stride;
     if (slots > want) slots = want;
-    if (!slots) { snprintf(t_err, sizeof t_err, "%s: not one table of %zu bytes fits the memory budget of %zu bytes (%zu in use)", what, stride, g_budget.load(), c.devBytes); return -LIZARDGPU_ERR_NOMEM; }
-    const int rc = dev_alloc(c, (void**)at, slots * stride, what);
+    if (!slots) { snprintf(t_err, sizeof t_err, "%s: not one table of %zu bytes fits the memory budget of %zu bytes (%zu in use)", kTableWhat[k], stride, g_budget.load(), c.devBytes); return -LIZARDGPU_ERR_NOMEM; }
+    const int rc = dev_alloc(c, (void**)&x.tables[k], slots * stride, kTableWhat[k]);
     if (rc) return rc;
-    *slotsAt = slots;
+    x.tableSlots[k] = slots;
     return 0;
 }
 
@@ -267,16 +275,175 @@ int clamp_level(int level)                                       // reference li
     return level;
 }
 
-// Largest block the GPU path takes at a level (0 = level not on the GPU path).  The table forms of the fast and priceFast
-// parsers keep positions modulo a power of two and sweep (lz_block.h, lz_pricefast.h): any size the reference takes
-// (lib/lizard_compress.h:121).  hashChain keeps full positions; its per-wave work area grows with the block (launch()).
-// hashChain (13-17 / 34-38) and noChain (12 / 32 / 33: the same kernels with one candidate per search, lz_hashchain.h)
-bool hc_level(int lv) { return (lv >= 12 && lv <= 17) || (lv >= 32 && lv <= 38); }
+// What a level runs: one row per clamped level and block-size range (the rows of a level in ascending maxBlock; the first that
+// takes the block size is the one).  A level without a row is not on the GPU path.  Everything the launcher and the getters know
+// about a level comes from here.
+struct LevelRow {
+    int    level;
+    size_t maxBlock;
+    void (*enqueue)(dim3 grid, dim3 block, hipStream_t stream, const LzBatch& a);
+    u32    W;                 // waves of a workgroup (one workgroup per CU)
+    u32    perGroup;          // of which claim blocks: W, but for the producer / consumer form
+    TableClass tables;        // per-wave tables in global memory
+    bool   laneOrder;         // relies on "lanes of one LDS atomic are served in lane order" (the self-check of ctx_init_body)
+    bool   needBest;          // hashChain work areas with best[] (first searches decided ahead of the parse)
+};
+template <void (*K)(LzBatch)>
+void enqueue_kernel(dim3 grid, dim3 block, hipStream_t stream, const LzBatch& a) { hipLaunchKernelGGL(K, grid, block, 0, stream, a); }
+template <void (*K)(LzBatch)>                                    // the row of kernel instantiation K
+constexpr LevelRow row(int level, size_t maxBlock, u32 W, u32 perGroup, TableClass tables, bool laneOrder = false, bool needBest = false)
+{
+    return { level, maxBlock, enqueue_kernel<K>, W, perGroup, tables, laneOrder, needBest };
+}
 
+// The table forms of the fast and priceFast parsers keep positions modulo a power of two and sweep (lz_block.h, lz_pricefast.h): any
+// size the reference takes (lib/lizard_compress.h:121).  hashChain keeps full positions; its work areas grow with the block.
+const size_t kAnyBlock = (size_t)LIZARD_MAX_INPUT_SIZE;
+// hashChain (13-17 / 34-38) and noChain (12 / 32 / 33: the same kernels with one candidate per search, lz_hashchain.h).  The
+// arbitration follows the template argument, searchNum the run-time level: the two are tied here.
+template <int LEVEL, int SEARCHLEN, int HLOG = 18>
+constexpr LevelRow hc_row()
+{
+    constexpr bool HUF = LEVEL >= 30;
+    constexpr int lv = LEVEL >= 32 ? LEVEL - 21 : LEVEL;         // 33 .. 38 are the twins of 12 .. 17; 32 is noChain too
+    static_assert(SEARCHLEN == (lv <= 12 ? 6 : lv <= 15 ? lv - 6 : 4), "noChain levels 12/32/33 run <*, 6>, levels 13/14/15 and twins <*, 7/8/9>, the rest <*, 4>");
+    return row<lz_hashchain_kernel<HUF, SEARCHLEN, HLOG>>(LEVEL, kAnyBlock, LZ_WAVES_HC, LZ_WAVES_HC, kHashChain, true, lv >= 16);
+}
+static_assert(LZ_PF_SLOT_BYTES >= (4u << 14), "levels 20/40 keep 2^14 u32 slots per wave in the 64 KiB slots of levels 21/41");
+const LevelRow kLevels[] = {
+#if LZ_FAST12_SPLIT                                              // (the producer / consumer form keeps every table in LDS)
+    row<lz_fast12_split_kernel<false>>(10, kAnyBlock, LZ_SPLIT_PROD + LZ_SPLIT_CONS, LZ_SPLIT_PROD, kNoTables, true),
+    row<lz_fast12_split_kernel<true>>(30, kAnyBlock, LZ_SPLIT_PROD_HUF + LZ_SPLIT_CONS_HUF, LZ_SPLIT_PROD_HUF, kNoTables, true),
+#else                                                            // (tuning builds; global-table waves hold 22-bit positions: blocks up to 4 MiB)
+    row<lz_fast12_kernel<false, true>>(10, 4u << 20, LZ_WAVES_FAST, LZ_WAVES_FAST, kPf64k, true),
+    row<lz_fast12_kernel<false, false>>(10, kAnyBlock, LZ_WAVES_FASTLDS, LZ_WAVES_FASTLDS, kPf64k, true),
+    row<lz_fast12_kernel<true, true>>(30, 4u << 20, LZ_WAVES_FAST_HUF, LZ_WAVES_FAST_HUF, kPf64k, true),
+    row<lz_fast12_kernel<true, false>>(30, kAnyBlock, LZ_WAVES_FASTLDS_HUF, LZ_WAVES_FASTLDS_HUF, kPf64k, true),
+#endif
+    row<lz_fast18_kernel<false>>(11, kAnyBlock, LZ_WAVES_FAST18, LZ_WAVES_FAST18, kWide18),
+    row<lz_fast18_kernel<true>>(31, kAnyBlock, LZ_WAVES_FAST18, LZ_WAVES_FAST18, kWide18),
+    hc_row<12, 6>(), hc_row<13, 7>(), hc_row<14, 8>(), hc_row<15, 9>(), hc_row<16, 4>(), hc_row<17, 4>(),
+    hc_row<32, 6, 14>(), hc_row<33, 6>(), hc_row<34, 7>(), hc_row<35, 8>(), hc_row<36, 9>(), hc_row<37, 4>(), hc_row<38, 4>(),
+    row<lz_fastbig14_kernel<false>>(20, kAnyBlock, LZ_WAVES_FASTBIG, LZ_WAVES_FASTBIG, kPf64k),
+    row<lz_fastbig14_kernel<true>>(40, kAnyBlock, LZ_WAVES_FASTBIG, LZ_WAVES_FASTBIG, kPf64k),
+    row<lz_pricefast18_kernel<false>>(22, kAnyBlock, LZ_PF22_W, LZ_PF22_W, kWide18),
+    row<lz_pricefast18_kernel<true>>(42, kAnyBlock, LZ_PF22_W, LZ_PF22_W, kWide18),
+    row<lz_pricefast14_kernel<false, true>>(21, 256u << 10, LZ_PF18_W, LZ_PF18_W, kPf64k),      // 18-bit LDS tables
+    row<lz_pricefast14_kernel<false, false>>(21, kAnyBlock, LZ_PF_W, LZ_PF_W, kPf64k),
+    row<lz_pricefast14_kernel<true, true>>(41, 256u << 10, LZ_PF18_W_HUF, LZ_PF18_W_HUF, kPf64k),
+    row<lz_pricefast14_kernel<true, false>>(41, kAnyBlock, LZ_PF_W, LZ_PF_W, kPf64k),
+};
+const LevelRow* find_row(int lv, size_t blockSize)
+{
+    for (const LevelRow& r : kLevels) if (r.level == lv && blockSize <= r.maxBlock) return &r;
+    return nullptr;
+}
+// Largest block the GPU path takes at a level (0 = level not on the GPU path).
 size_t level_max_block(int lv)
 {
-    const bool hcLevel = hc_level(lv);
-    if (lv == 10 || lv == 30 || lv == 11 || lv == 31 || lv == 20 || lv == 40 || lv == 21 || lv == 41 || lv == 22 || lv == 42 || hcLevel) return (size_t)LIZARD_MAX_INPUT_SIZE;
+    size_t m = 0;
+    for (const LevelRow& r : kLevels) if (r.level == lv && r.maxBlock > m) m = r.maxBlock;
+    return m;
+}
+
+// Which arena?  (lizard_gpu_ctx.h, LzArena.)  The context's own unless this is a small launch (`eligible`: fewer blocks than the
+// machine has claiming waves, not hashChain) on another stream than the one that used it last and that launch is still running;
+// then: an extra arena last used by this stream, or an idle one, or a new one, or — all busy, none left to make — the extra ones
+// in turn.
+LzArena* pick_arena(Ctx& c, bool eligible, hipStream_t stream)
+{
+    LzArena& own = c.arena[0];
+    LzArena* ar = nullptr;
+    if (eligible && c.maxArenas > 1 && own.timed && own.lastStream != stream && hipEventQuery(own.ev1) != hipSuccess) {
+        for (int i = 1; i < c.nArenas && !ar; i++) if (c.arena[i].lastStream == stream) ar = &c.arena[i];
+        for (int i = 1; i < c.nArenas && !ar; i++) if (!c.arena[i].timed || hipEventQuery(c.arena[i].ev1) == hipSuccess) ar = &c.arena[i];   // (anything but success: busy)
+        if (!ar && c.nArenas < c.maxArenas && budget_room(c) >= (size_t)c.cus * kScratchBytes) {
+            LzArena& x = c.arena[c.nArenas];
+            if (arena_create(c, x) == 0) {
+                ar = &x; c.nArenas++;
+                if (getenv("LIZARDGPU_VERBOSE")) fprintf(stderr, "liblizard_amd: device %d: arena %d for small launches on concurrent streams (LIZARDGPU_ARENAS caps them)\n", c.device, c.nArenas);
+            } else { arena_destroy(c, x); t_err[0] = 0; }        // no room: share the context's own after all
+        }
+        if (!ar && c.nArenas > 1) { ar = &c.arena[1 + c.nextExtra % (c.nArenas - 1)]; c.nextExtra++; }
+        (void)hipGetLastError();                                 // (hipEventQuery's "not ready" is not an error to report)
+    }
+    // extra arenas that no launch has asked for in a while go back (64 launches on the context's own arena, all of theirs finished)
+    if (ar) { c.idleLaunches = 0; return ar; }
+    if (c.nArenas > 1 && eligible && ++c.idleLaunches >= 64) {   // (launches that could have asked for one: large and hashChain launches say nothing about the small streams)
+        bool idle = true;
+        for (int i = 1; i < c.nArenas; i++) if (c.arena[i].timed && hipEventQuery(c.arena[i].ev1) != hipSuccess) idle = false;
+        (void)hipGetLastError();
+        if (idle) free_extra_arenas(c);
+        c.idleLaunches = 0;
+    }
+    return &own;
+}
+
+// The per-wave tables of class k in *ar, allocated on first use.  An extra arena whose tables do not fit the memory budget any
+// more (the hashChain work areas or the context's own tables took the room): the launch goes to the context's own arena after
+// all — it waits for the launch that holds it, and may give up what other levels left behind — instead of failing where it
+// would have succeeded on a quiet device.
+int ensure_arena_tables(Ctx& c, LzArena*& ar, TableClass k)
+{
+    if (!ar->tables[k] && ar != &c.arena[0] && alloc_table_slots(c, *ar, k)) { (void)hipGetLastError(); ar = &c.arena[0]; }
+    return ar->tables[k] ? 0 : alloc_table_slots(c, *ar, k);
+}
+
+// The hashChain work areas (the context's, not an arena's).  Per wave: bins, links, and 6 bytes + 1 bit per block position (chain,
+// packed chain words, hit bits) — 10 bytes at levels 16/17/37/38, whose first searches are decided ahead of the parse (best[],
+// the LAST array of the slot: the other levels' slots simply end before it).  One slot per resident wave while that fits in
+// about half of the free memory (256 KiB blocks: 14 GiB, 18 GiB with best[]; 4 MiB blocks: 110 GiB, or as many slots as fit under
+// the 128 GiB cap with best[]); larger blocks get as many slots as fit and the other waves leave (lz_wave_main).
+int ensure_hc_slots(Ctx& c, int lv, size_t blockSize, bool needBest)
+{
+    const size_t cap = (blockSize + 65535u) & ~(size_t)65535u;
+    if (c.hcSlots && c.hcMaxBlock >= cap && (!needBest || c.hcHasBest)) return 0;
+    const bool withBest = needBest || c.hcHasBest;
+    const size_t capA = cap > c.hcMaxBlock ? cap : c.hcMaxBlock;                 // (a re-allocation never shrinks what the slots take)
+    const size_t slotBytes = LZ_HC_SLOT_BYTES(capA) - (withBest ? 0u : 4u * capA);
+    if (c.hcSlots) { LZ_HIP(hipDeviceSynchronize()); dev_free(c, c.hcSlots, c.hcNSlots * c.hcSlotBytes); c.hcSlots = nullptr; c.hcNSlots = 0; }
+    size_t freeB = 0, totalB = 0;
+    LZ_HIP(hipMemGetInfo(&freeB, &totalB));
+    size_t budget = freeB / 2u;
+    if (budget > ((size_t)128 << 30)) budget = (size_t)128 << 30;
+    if (g_budget.load(std::memory_order_relaxed)) {      // LizardGPU_setMemoryBudget: what other levels left behind goes first
+        if (budget_room(c) < (size_t)c.cus * LZ_MAX_WAVES * slotBytes) free_tables_except(c, kHashChain);
+        if (budget > budget_room(c)) budget = budget_room(c);
+    }
+    // LIZARDGPU_HC_WORKAREA_MB caps the reservation (a caller that shares the device with other allocations); fewer work
+    // areas than resident waves only means fewer hashChain blocks in flight (the waves without one leave)
+    if (const char* e = getenv("LIZARDGPU_HC_WORKAREA_MB")) {
+        const size_t mb = (size_t)strtoull(e, nullptr, 10);
+        if (mb > 0 && (mb << 20) < budget) budget = mb << 20;
+    }
+    size_t nSlots = budget / slotBytes;
+    if (nSlots > (size_t)c.cus * LZ_MAX_WAVES) nSlots = (size_t)c.cus * LZ_MAX_WAVES;
+    if (nSlots == 0) { snprintf(t_err, sizeof t_err, "level %d: no room for a hashChain work area of %zu bytes", lv, slotBytes); return -LIZARDGPU_ERR_NOMEM; }
+    { const int rc_ = dev_alloc(c, (void**)&c.hcSlots, nSlots * slotBytes, "hashChain work areas"); if (rc_) return rc_; }
+    c.hcMaxBlock = capA; c.hcNSlots = nSlots; c.hcHasBest = withBest; c.hcSlotBytes = slotBytes;
+    if (getenv("LIZARDGPU_VERBOSE"))
+        fprintf(stderr, "liblizard_amd: device %d: hashChain levels reserve %zu work areas of %zu bytes (%.1f GiB of %.1f GiB free; LIZARDGPU_HC_WORKAREA_MB caps it)\n",
+                c.device, nSlots, slotBytes, (double)(nSlots * slotBytes) / (double)(1u << 30), (double)freeB / (double)(1u << 30));
+    return 0;
+}
+
+// One kernel on arena x.  The scratch arena, the tables and the block counter of an arena are shared by all its launches: a
+// launch on another stream first waits (on the GPU) for the previous one to finish (always, also on the stream that used the
+// arena last: a destroyed stream's handle can come back for a new stream, and a same-stream wait costs nothing).  k0 / k1 (may be
+// null) are recorded around the kernel.
+template <class Launch>
+int enqueue_on(Ctx& c, LzArena& x, hipStream_t stream, hipEvent_t k0, hipEvent_t k1, Launch launchKernel)
+{
+    if (x.timed) LZ_HIP(hipStreamWaitEvent(stream, x.ev1, 0));
+    LZ_HIP(hipMemsetAsync(x.counter, 0, 4, stream));
+    LZ_HIP(hipEventRecord(x.ev0, stream));
+    if (k0) LZ_HIP(hipEventRecord(k0, stream));
+    launchKernel();
+    LZ_HIP(hipGetLastError());
+    LZ_HIP(hipEventRecord(x.ev1, stream));
+    if (k1) LZ_HIP(hipEventRecord(k1, stream));
+    x.timed = 1; x.lastStream = stream;
+    c.lastEv0 = x.ev0; c.lastEv1 = x.ev1;
     return 0;
 }
 
@@ -287,204 +454,53 @@ int launch(Ctx& c, const void* d_src, size_t nBlocks, size_t blockSize, size_t l
            const u32* d_srcSizes = nullptr, const u64* d_srcOffsets = nullptr)
 {
     const int lv = clamp_level(level);
-    if (!LizardGPU_levelSupported(lv)) { snprintf(t_err, sizeof t_err, "level %d has no GPU kernel", lv); return -LIZARDGPU_ERR_LEVEL; }
+    if (!level_max_block(lv)) { snprintf(t_err, sizeof t_err, "level %d has no GPU kernel", lv); return -LIZARDGPU_ERR_LEVEL; }
     if (!d_src || !d_dst || !d_sizes || nBlocks == 0 || nBlocks > 0xFFFFFFFFu || blockSize == 0 || blockSize > LIZARD_MAX_INPUT_SIZE
         || lastBlockSize == 0 || lastBlockSize > blockSize || dstStride < (size_t)LIZARD_COMPRESSBOUND((int)blockSize)) {
         snprintf(t_err, sizeof t_err, "bad argument (null pointer, zero size, lastBlockSize > blockSize or dstStride < Lizard_compressBound)");
         return -LIZARDGPU_ERR_ARG;
     }
-    if (blockSize > level_max_block(lv)) {
+    const LevelRow* const row = find_row(lv, blockSize);
+    if (!row) {
         snprintf(t_err, sizeof t_err, "level %d: blocks above %zu bytes are not supported on the GPU path", lv, level_max_block(lv));
         return -LIZARDGPU_ERR_ARG;
     }
     int rc = ctx_init(c);
     if (rc) return rc;
-    if (!c.laneOrderOk && (lv == 10 || lv == 30 || hc_level(lv))) {
+    if (!c.laneOrderOk && row->laneOrder) {
         snprintf(t_err, sizeof t_err, "level %d refused: device %d failed the self-check \"lanes of one LDS atomic are served in lane order\" its kernel relies on", lv, c.device);
         return -LIZARDGPU_ERR_HARDWARE;
     }
+    const bool smallLaunch = nBlocks < (size_t)c.cus * row->perGroup;
+    LzArena* ar = pick_arena(c, smallLaunch && row->tables != kHashChain, stream);
     LzBatch a;
     a.src = (const u8*)d_src; a.blockSize = blockSize; a.nBlocks = (u32)nBlocks; a.lastBlockSize = (u32)lastBlockSize;
     a.dst = (u8*)d_dst; a.dstStride = dstStride; a.sizes = d_sizes; a.level = (u32)lv;
-    a.scratch = c.scratch; a.counter = c.counter; a.tables = nullptr; a.tableStride = 0; a.tableSlots = 0xFFFFFFFFu;
+    a.tables = nullptr; a.tableStride = 0; a.tableSlots = 0xFFFFFFFFu;
     a.srcSizes = d_srcSizes; a.srcOffsets = d_srcOffsets; a.activeWaves = 0xFFFFFFFFu;
-    // one workgroup of W waves per CU; small batches launch only as many workgroups as they have blocks for
-    const bool hcLevel = hc_level(lv);
-    const bool fastMixed = blockSize <= (4u << 20);                         // global-table waves hold 22-bit positions
-    const bool pfSmall = blockSize <= (256u << 10);                         // 18-bit LDS tables
-    const bool huf = lv >= 30;
-    u32 W;
-    u32 perGroup = 0;                                                        // blocks in flight per workgroup when that is not W (producer / consumer form)
-    if ((lv == 10 || lv == 30) && LZ_FAST12_SPLIT) { W = huf ? LZ_SPLIT_PROD_HUF + LZ_SPLIT_CONS_HUF : LZ_SPLIT_PROD + LZ_SPLIT_CONS; perGroup = huf ? LZ_SPLIT_PROD_HUF : LZ_SPLIT_PROD; }
-    else if (lv == 10 || lv == 30) W = fastMixed ? (huf ? LZ_WAVES_FAST_HUF : LZ_WAVES_FAST) : (huf ? LZ_WAVES_FASTLDS_HUF : LZ_WAVES_FASTLDS);
-    else if (lv == 11 || lv == 31) W = LZ_WAVES_FAST18;
-    else if (hcLevel)              W = LZ_WAVES_HC;
-    else if (lv == 21 || lv == 41) W = pfSmall ? (huf ? LZ_PF18_W_HUF : LZ_PF18_W) : LZ_PF_W;
-    else if (lv == 20 || lv == 40) W = LZ_WAVES_FASTBIG;
-    else                           W = LZ_PF22_W;
-    if (!perGroup) perGroup = W;
-    // Which arena?  (lizard_gpu_ctx.h, LzArena.)  The context's own unless this is a small launch on another stream than the one
-    // that used it last and that launch is still running; then: an extra arena last used by this stream, or an idle one, or a new
-    // one, or — all busy, none left to make — the extra ones in turn.
-    LzArena* ar = nullptr;                                                   // nullptr: the context's own
-    const bool smallLaunch = nBlocks < (size_t)c.cus * perGroup;
-    if (smallLaunch && !hcLevel && c.maxArenas > 1 && c.timed && c.lastStream != stream && hipEventQuery(c.ev1) != hipSuccess) {
-        for (int i = 0; i < c.nExtra && !ar; i++) if (c.extra[i].lastStream == stream) ar = &c.extra[i];
-        for (int i = 0; i < c.nExtra && !ar; i++) if (!c.extra[i].timed || hipEventQuery(c.extra[i].ev1) == hipSuccess) ar = &c.extra[i];   // (anything but success: busy)
-        if (!ar && c.nExtra < c.maxArenas - 1 && budget_room(c) >= (size_t)c.cus * kScratchBytes) {
-            LzArena& x = c.extra[c.nExtra];
-            memset(&x, 0, sizeof x);
-            hipError_t e = hipMalloc((void**)&x.scratch, (size_t)c.cus * kScratchBytes);
-            if (e == hipSuccess) c.devBytes += (size_t)c.cus * kScratchBytes;
-            if (e == hipSuccess) e = hipMalloc((void**)&x.counter, 64);
-            if (e == hipSuccess) e = hipEventCreate(&x.ev0);
-            if (e == hipSuccess) e = hipEventCreate(&x.ev1);
-            if (e == hipSuccess) {
-                ar = &x; c.nExtra++;
-                if (getenv("LIZARDGPU_VERBOSE")) fprintf(stderr, "liblizard_amd: device %d: arena %d for small launches on concurrent streams (LIZARDGPU_ARENAS caps them)\n", c.device, c.nExtra + 1);
-            } else {                                                         // no room: share the context's own after all
-                (void)hipGetLastError();
-                dev_free(c, x.scratch, (size_t)c.cus * kScratchBytes);
-                if (x.counter) (void)hipFree(x.counter);
-                if (x.ev0) (void)hipEventDestroy(x.ev0);
-                if (x.ev1) (void)hipEventDestroy(x.ev1);
-                memset(&x, 0, sizeof x);
-            }
-        }
-        if (!ar && c.nExtra) { ar = &c.extra[c.nextExtra % c.nExtra]; c.nextExtra++; }
-        (void)hipGetLastError();                                             // (hipEventQuery's "not ready" is not an error to report)
-    }
-    // extra arenas that no launch has asked for in a while go back (64 launches on the context's own arena, all of theirs finished)
-    if (ar) c.idleLaunches = 0;
-    else if (c.nExtra && smallLaunch && !hcLevel && ++c.idleLaunches >= 64) {   // (launches that could have asked for one: large and hashChain launches say nothing about the small streams)
-        bool idle = true;
-        for (int i = 0; i < c.nExtra; i++) if (c.extra[i].timed && hipEventQuery(c.extra[i].ev1) != hipSuccess) idle = false;
-        (void)hipGetLastError();
-        if (idle) free_extra_arenas(c);
-        c.idleLaunches = 0;
-    }
-    uint8_t** tablesAt = ar ? &ar->tables : &c.tables;
-    uint8_t** pfTablesAt = ar ? &ar->pfTables : &c.pfTables;
-    size_t* tablesSlotsAt = ar ? &ar->tablesSlots : &c.tablesSlots;
-    size_t* pfSlotsAt = ar ? &ar->pfSlots : &c.pfSlots;
-    if (ar) { a.scratch = ar->scratch; a.counter = ar->counter; }
-    // An extra arena whose tables do not fit the memory budget any more (the hashChain work areas or the context's own tables took
-    // the room): the launch goes to the context's own arena after all — it waits for the launch that holds it, and may give up
-    // what other levels left behind (ownArena) — instead of failing where it would have succeeded on a quiet device.
-    auto own_arena_after_all = [&]() {
-        (void)hipGetLastError();
-        ar = nullptr; a.scratch = c.scratch; a.counter = c.counter;
-        tablesAt = &c.tables; pfTablesAt = &c.pfTables; tablesSlotsAt = &c.tablesSlots; pfSlotsAt = &c.pfSlots;
-    };
-    if (hcLevel) {
-        // per wave: bins, links, and 6 bytes + 1 bit per block position (chain, packed chain words, hit bits) — 10 bytes at levels
-        // 16/17/37/38, whose first searches are decided ahead of the parse (best[], the LAST array of the slot: the other levels'
-        // slots simply end before it).  One slot per resident wave while that fits in about half of the free memory (256 KiB
-        // blocks: 14 GiB, 18 GiB with best[]; 4 MiB blocks: 110 GiB, or as many slots as fit under the 128 GiB cap with best[]);
-        // larger blocks get as many slots as fit and the other waves leave (lz_wave_main).
-        const size_t cap = (blockSize + 65535u) & ~(size_t)65535u;
-        const bool needBest = lv == 16 || lv == 17 || lv == 37 || lv == 38;
-        if (!c.hcSlots || c.hcMaxBlock < cap || (needBest && !c.hcHasBest)) {
-            const bool withBest = needBest || c.hcHasBest;
-            const size_t capA = cap > c.hcMaxBlock ? cap : c.hcMaxBlock;                 // (a re-allocation never shrinks what the slots take)
-            const size_t slotBytes = LZ_HC_SLOT_BYTES(capA) - (withBest ? 0u : 4u * capA);
-            if (c.hcSlots) { LZ_HIP(hipDeviceSynchronize()); dev_free(c, c.hcSlots, c.hcNSlots * c.hcSlotBytes); c.hcSlots = nullptr; c.hcNSlots = 0; }
-            size_t freeB = 0, totalB = 0;
-            LZ_HIP(hipMemGetInfo(&freeB, &totalB));
-            size_t budget = freeB / 2u;
-            if (budget > ((size_t)128 << 30)) budget = (size_t)128 << 30;
-            if (g_budget.load(std::memory_order_relaxed)) {      // LizardGPU_setMemoryBudget: what other levels left behind goes first
-                if (budget_room(c) < (size_t)c.cus * LZ_MAX_WAVES * slotBytes) free_tables_except(c, 3);
-                if (budget > budget_room(c)) budget = budget_room(c);
-            }
-            // LIZARDGPU_HC_WORKAREA_MB caps the reservation (a caller that shares the device with other allocations); fewer work
-            // areas than resident waves only means fewer hashChain blocks in flight (the waves without one leave)
-            if (const char* e = getenv("LIZARDGPU_HC_WORKAREA_MB")) {
-                const size_t mb = (size_t)strtoull(e, nullptr, 10);
-                if (mb > 0 && (mb << 20) < budget) budget = mb << 20;
-            }
-            size_t nSlots = budget / slotBytes;
-            if (nSlots > (size_t)c.cus * LZ_MAX_WAVES) nSlots = (size_t)c.cus * LZ_MAX_WAVES;
-            if (nSlots == 0) { snprintf(t_err, sizeof t_err, "level %d: no room for a hashChain work area of %zu bytes", lv, slotBytes); return -LIZARDGPU_ERR_NOMEM; }
-            { const int rc_ = dev_alloc(c, (void**)&c.hcSlots, nSlots * slotBytes, "hashChain work areas"); if (rc_) return rc_; }
-            c.hcMaxBlock = capA; c.hcNSlots = nSlots; c.hcHasBest = withBest; c.hcSlotBytes = slotBytes;
-            if (getenv("LIZARDGPU_VERBOSE"))
-                fprintf(stderr, "liblizard_amd: device %d: hashChain levels reserve %zu work areas of %zu bytes (%.1f GiB of %.1f GiB free; LIZARDGPU_HC_WORKAREA_MB caps it)\n",
-                        c.device, nSlots, slotBytes, (double)(nSlots * slotBytes) / (double)(1u << 30), (double)freeB / (double)(1u << 30));
-        }
+    if (row->tables == kHashChain) {
+        if ((rc = ensure_hc_slots(c, lv, blockSize, row->needBest))) return rc;
         a.tables = c.hcSlots; a.tableStride = c.hcSlotBytes; a.tableSlots = (u32)c.hcNSlots;
-    } else if (lv == 11 || lv == 31 || lv == 22 || lv == 42) {
-        if (!*tablesAt && ar && alloc_table_slots(c, tablesAt, tablesSlotsAt, LZ_TABWIDE_BYTES(18), 1, false, "tables of levels 11/31/22/42")) own_arena_after_all();
-        if (!*tablesAt && (rc = alloc_table_slots(c, tablesAt, tablesSlotsAt, LZ_TABWIDE_BYTES(18), 1, !ar, "tables of levels 11/31/22/42"))) return rc;
-        a.tables = *tablesAt; a.tableStride = LZ_TABWIDE_BYTES(18); a.tableSlots = (u32)*tablesSlotsAt;
-    } else if (!((lv == 10 || lv == 30) && LZ_FAST12_SPLIT)) {             // (the producer / consumer form keeps every table in LDS)
-        if (!*pfTablesAt && ar && alloc_table_slots(c, pfTablesAt, pfSlotsAt, LZ_PF_SLOT_BYTES, 2, false, "tables of levels 21/41")) own_arena_after_all();
-        if (!*pfTablesAt && (rc = alloc_table_slots(c, pfTablesAt, pfSlotsAt, LZ_PF_SLOT_BYTES, 2, !ar, "tables of levels 21/41"))) return rc;
-        a.tables = *pfTablesAt; a.tableStride = LZ_PF_SLOT_BYTES; a.tableSlots = (u32)*pfSlotsAt;
+    } else if (row->tables != kNoTables) {
+        const TableClass k = row->tables;
+        if ((rc = ensure_arena_tables(c, ar, k))) return rc;
+        a.tables = ar->tables[k]; a.tableStride = kTableStride[k]; a.tableSlots = (u32)ar->tableSlots[k];
     }
-    u32 grid = (u32)((nBlocks + perGroup - 1) / perGroup);
+    a.scratch = ar->scratch; a.counter = ar->counter;
+    // one workgroup of W waves per CU; small batches launch only as many workgroups as they have blocks for
+    u32 grid = (u32)((nBlocks + row->perGroup - 1) / row->perGroup);
     if (grid > (u32)c.cus) grid = (u32)c.cus;
 #if LZ_SPREAD_SMALL
     // A launch with fewer blocks than the chip has block-claiming waves is spread over ALL CUs, ceil(nBlocks / grid) claiming
     // waves per workgroup, instead of filling nBlocks / perGroup CUs to the brim: 256 blocks are 256 CUs x 1 wave, not 20 x 13.
-    if (nBlocks < (size_t)c.cus * perGroup) {
+    if (smallLaunch) {
         grid = nBlocks < (size_t)c.cus ? (u32)nBlocks : (u32)c.cus;
         a.activeWaves = (u32)((nBlocks + grid - 1) / grid);
     }
 #endif
-    // The scratch arena, the tables and the block counter are shared by all launches on this device: a launch
-    // on another stream first waits (on the GPU) for the previous one to finish.
-    hipEvent_t const e0 = ar ? ar->ev0 : c.ev0, e1 = ar ? ar->ev1 : c.ev1;
-    // (always, also on the stream that used the arena last: a destroyed stream's handle can come back for a new stream, and a
-    //  same-stream wait costs nothing)
-    if (ar ? ar->timed != 0 : c.timed != 0) LZ_HIP(hipStreamWaitEvent(stream, e1, 0));
-    LZ_HIP(hipMemsetAsync(a.counter, 0, 4, stream));
-    LZ_HIP(hipEventRecord(e0, stream));
-    if (k0) LZ_HIP(hipEventRecord(k0, stream));
-    const dim3 g(grid), t(64 * W);
-    switch (lv) {
-#if LZ_FAST12_SPLIT
-    case 10: hipLaunchKernelGGL(lz_fast12_split_kernel<false>, g, t, 0, stream, a); break;
-    case 30: hipLaunchKernelGGL(lz_fast12_split_kernel<true>, g, t, 0, stream, a); break;
-#else
-    case 10: if (fastMixed) hipLaunchKernelGGL((lz_fast12_kernel<false, true>), g, t, 0, stream, a);
-             else           hipLaunchKernelGGL((lz_fast12_kernel<false, false>), g, t, 0, stream, a);
-             break;
-    case 30: if (fastMixed) hipLaunchKernelGGL((lz_fast12_kernel<true, true>), g, t, 0, stream, a);
-             else           hipLaunchKernelGGL((lz_fast12_kernel<true, false>), g, t, 0, stream, a);
-             break;
-#endif
-    case 11: hipLaunchKernelGGL(lz_fast18_kernel<false>, g, t, 0, stream, a); break;
-    case 31: hipLaunchKernelGGL(lz_fast18_kernel<true>, g, t, 0, stream, a); break;
-    case 12:                   hipLaunchKernelGGL((lz_hashchain_kernel<false, 6>), g, t, 0, stream, a); break;
-    case 13:                   hipLaunchKernelGGL((lz_hashchain_kernel<false, 7>), g, t, 0, stream, a); break;
-    case 14:                   hipLaunchKernelGGL((lz_hashchain_kernel<false, 8>), g, t, 0, stream, a); break;
-    case 15:                   hipLaunchKernelGGL((lz_hashchain_kernel<false, 9>), g, t, 0, stream, a); break;
-    case 16: case 17:          hipLaunchKernelGGL((lz_hashchain_kernel<false, 4>), g, t, 0, stream, a); break;
-    case 32:                   hipLaunchKernelGGL((lz_hashchain_kernel<true, 6, 14>), g, t, 0, stream, a); break;
-    case 33:                   hipLaunchKernelGGL((lz_hashchain_kernel<true, 6>), g, t, 0, stream, a); break;
-    case 34:                   hipLaunchKernelGGL((lz_hashchain_kernel<true, 7>), g, t, 0, stream, a); break;
-    case 35:                   hipLaunchKernelGGL((lz_hashchain_kernel<true, 8>), g, t, 0, stream, a); break;
-    case 36:                   hipLaunchKernelGGL((lz_hashchain_kernel<true, 9>), g, t, 0, stream, a); break;
-    case 37: case 38:          hipLaunchKernelGGL((lz_hashchain_kernel<true, 4>), g, t, 0, stream, a); break;
-    case 20: hipLaunchKernelGGL(lz_fastbig14_kernel<false>, g, t, 0, stream, a); break;
-    case 40: hipLaunchKernelGGL(lz_fastbig14_kernel<true>, g, t, 0, stream, a); break;
-    case 22: hipLaunchKernelGGL(lz_pricefast18_kernel<false>, g, t, 0, stream, a); break;
-    case 42: hipLaunchKernelGGL(lz_pricefast18_kernel<true>, g, t, 0, stream, a); break;
-    case 21: if (pfSmall) hipLaunchKernelGGL((lz_pricefast14_kernel<false, true>), g, t, 0, stream, a);
-             else         hipLaunchKernelGGL((lz_pricefast14_kernel<false, false>), g, t, 0, stream, a);
-             break;
-    default: if (pfSmall) hipLaunchKernelGGL((lz_pricefast14_kernel<true, true>), g, t, 0, stream, a);
-             else         hipLaunchKernelGGL((lz_pricefast14_kernel<true, false>), g, t, 0, stream, a);
-             break;
-    }
-    LZ_HIP(hipGetLastError());
-    LZ_HIP(hipEventRecord(e1, stream));
-    if (k1) LZ_HIP(hipEventRecord(k1, stream));
-    if (ar) { ar->timed = 1; ar->lastStream = stream; } else { c.timed = true; c.lastStream = stream; }
-    c.lastEv0 = e0; c.lastEv1 = e1;
-    c.lastSplit = LZ_FAST12_SPLIT && (lv == 10 || lv == 30);
-    return 0;
+    rc = enqueue_on(c, *ar, stream, k0, k1, [&] { row->enqueue(dim3(grid), dim3(64 * row->W), stream, a); });
+    if (!rc) c.lastSplit = row->perGroup != row->W;              // (only the producer / consumer form has waves that claim no block)
+    return rc;
 }
 
 int launch_decompress(Ctx& c, const void* d_src, const u64* d_offsets, size_t srcStride, const u32* d_srcSizes, size_t nBlocks,
@@ -496,21 +512,15 @@ int launch_decompress(Ctx& c, const void* d_src, const u64* d_offsets, size_t sr
     }
     int rc = ctx_init(c);
     if (rc) return rc;
+    LzArena& own = c.arena[0];                                   // scratch arena and counter are shared with the compress launches
     LzUnBatch a;
     a.src = (const u8*)d_src; a.offsets = d_offsets; a.srcStride = srcStride; a.srcSizes = d_srcSizes;
     a.dst = (u8*)d_dst; a.dstStride = dstStride; a.outSizes = d_outSizes; a.nBlocks = (u32)nBlocks;
-    a.scratch = c.scratch; a.counter = c.counter;
+    a.scratch = own.scratch; a.counter = own.counter;
     u32 grid = (u32)((nBlocks + LZ_WAVES_DEC - 1) / LZ_WAVES_DEC);
     if (grid > (u32)c.cus) grid = (u32)c.cus;
-    if (c.timed) LZ_HIP(hipStreamWaitEvent(stream, c.ev1, 0));      // scratch arena and counter are shared with the compress launches
-    LZ_HIP(hipMemsetAsync(c.counter, 0, 4, stream));
-    LZ_HIP(hipEventRecord(c.ev0, stream));
-    hipLaunchKernelGGL(lz_decompress_kernel, dim3(grid), dim3(64 * LZ_WAVES_DEC), 0, stream, a);
-    LZ_HIP(hipGetLastError());
-    LZ_HIP(hipEventRecord(c.ev1, stream));
-    c.timed = true; c.lastStream = stream; c.lastEv0 = c.ev0; c.lastEv1 = c.ev1;
     c.hostKernelMs = -1.0f;
-    return 0;
+    return enqueue_on(c, own, stream, nullptr, nullptr, [&] { hipLaunchKernelGGL(lz_decompress_kernel, dim3(grid), dim3(64 * LZ_WAVES_DEC), 0, stream, a); });
 }
 
 // The records of one chunk of a frame (unframe_kernels.h).  Shares the context's own arena and counter with the compress launches
@@ -524,21 +534,15 @@ int launch_unframe(Ctx& c, const void* d_src, const u64* d_payloadOffsets, const
     }
     int rc = ctx_init(c);
     if (rc) return rc;
+    LzArena& own = c.arena[0];
     LzUnframeBatch a;
     a.src = (const u8*)d_src; a.payloadOffsets = d_payloadOffsets; a.words = d_words;
     a.slots = (u8*)d_slots; a.slotBytes = slotBytes; a.outSizes = d_outSizes; a.packSizes = d_packSizes; a.nRecords = (u32)nRecords;
-    a.scratch = c.scratch; a.counter = c.counter;
+    a.scratch = own.scratch; a.counter = own.counter;
     u32 grid = (u32)((nRecords + LZ_WAVES_DEC - 1) / LZ_WAVES_DEC);
     if (grid > (u32)c.cus) grid = (u32)c.cus;
-    if (c.timed) LZ_HIP(hipStreamWaitEvent(stream, c.ev1, 0));
-    LZ_HIP(hipMemsetAsync(c.counter, 0, 4, stream));
-    LZ_HIP(hipEventRecord(c.ev0, stream));
-    hipLaunchKernelGGL(lz_unframe_kernel, dim3(grid), dim3(64 * LZ_WAVES_DEC), 0, stream, a);
-    LZ_HIP(hipGetLastError());
-    LZ_HIP(hipEventRecord(c.ev1, stream));
-    c.timed = true; c.lastStream = stream; c.lastEv0 = c.ev0; c.lastEv1 = c.ev1;
     c.hostKernelMs = -1.0f;
-    return 0;
+    return enqueue_on(c, own, stream, nullptr, nullptr, [&] { hipLaunchKernelGGL(lz_unframe_kernel, dim3(grid), dim3(64 * LZ_WAVES_DEC), 0, stream, a); });
 }
 
 }  // namespace
@@ -583,7 +587,7 @@ int LizardGPU_residentWaves(void)
     Guard g;
     if (g.rc) return g.rc;
     int rc = ctx_init(*g.c);
-    return rc ? rc : g.c->cus * (LZ_FAST12_SPLIT ? LZ_SPLIT_PROD : LZ_WAVES_FAST);      // level-10 residency: blocks in flight = waves with a hash table (13 per CU, all in LDS)
+    return rc ? rc : g.c->cus * (int)find_row(10, 1)->perGroup;      // level-10 residency: blocks in flight = waves with a hash table (13 per CU, all in LDS)
 }
 
 static void release_all_contexts(size_t newBudget, bool setBudget)
@@ -651,7 +655,7 @@ int LizardGPU_trim(void)
         rc = g.rc;
         if (!rc && g.c->ready) {
             Ctx& c = *g.c;
-            free_tables_except(c, 0);
+            free_tables_except(c, kNoTables);
             for (Stage& s : c.stage) {
                 dev_free(c, s.d_in, s.d_in_cap); dev_free(c, s.d_slots, s.d_slots_cap); dev_free(c, s.d_packed, s.d_packed_cap);
                 s.d_in = s.d_slots = s.d_packed = nullptr; s.d_in_cap = s.d_slots_cap = s.d_packed_cap = 0;
@@ -699,7 +703,7 @@ int    lzk_dev_alloc(LzCtx* c, void** p, size_t bytes)
 {
     // staging of a host-buffer call (context locked by the caller): under a budget, the tables and work areas earlier launches left
     // behind make room for it (this call's own launch gets as many table slots as still fit)
-    if (bytes > budget_room(*c)) free_tables_except(*c, 0);
+    if (bytes > budget_room(*c)) free_tables_except(*c, kNoTables);
     return dev_alloc(*c, p, bytes, "staging buffer");
 }
 void   lzk_dev_free(LzCtx* c, void* p, size_t bytes) { dev_free(*c, p, bytes); }
@@ -754,9 +758,10 @@ int LizardGPU_profileDump(unsigned long long out[16])
         unsigned long long v[16];
         // the one-wave-per-block kernels keep a wave's record at the tail of its scratch slot; the producer / consumer kernels of
         // levels 10 / 30 (whose sequence buffers cover those tails) at the end of the workgroup's arena
-        const size_t group = (size_t)(w / LZ_MAX_WAVES) * LZ_MAX_WAVES * LZ_SCRATCH_BYTES;
-        u8* at = c.lastSplit ? c.scratch + group + (size_t)LZ_MAX_WAVES * LZ_SCRATCH_BYTES - (size_t)(w % LZ_MAX_WAVES + 1) * 128
-                             : c.scratch + (size_t)(w + 1) * LZ_SCRATCH_BYTES - 128;
+        const size_t group = (size_t)(w / LZ_MAX_WAVES) * kScratchBytes;
+        u8* const scratch = c.arena[0].scratch;
+        u8* at = c.lastSplit ? scratch + group + kScratchBytes - (size_t)(w % LZ_MAX_WAVES + 1) * 128
+                             : scratch + (size_t)(w + 1) * LZ_SCRATCH_BYTES - 128;
         if (hipMemcpy(v, at, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -LIZARDGPU_ERR_HIP;
         for (int k = 0; k < 15; k++) out[k] += v[k];
         (void)hipMemset(at, 0, sizeof v);
@@ -769,7 +774,7 @@ int LizardGPU_arenasInUse(void)
 {
     Guard g;
     if (g.rc) return 0;
-    return g.c->ready ? 1 + g.c->nExtra : 0;
+    return g.c->ready ? g.c->nArenas : 0;
 }
 
 float LizardGPU_lastKernelMs(void)
@@ -779,7 +784,7 @@ float LizardGPU_lastKernelMs(void)
     Ctx& c = *g.c;
     if (c.hostKernelMs >= 0.0f) return c.hostKernelMs;
     float ms = -1.0f;
-    if (c.lastEv1 && c.timed && hipEventSynchronize(c.lastEv1) == hipSuccess) {
+    if (c.lastEv1 && c.arena[0].timed && hipEventSynchronize(c.lastEv1) == hipSuccess) {
         if (hipEventElapsedTime(&ms, c.lastEv0, c.lastEv1) != hipSuccess) ms = -1.0f;
     }
     return ms;

@@ -47,15 +47,17 @@ typedef struct LzCombine {
 } LzCombine;
 
 /* A scratch arena with its block counter and the per-wave tables of the levels that keep them in global memory.  Every launch
- * needs one to itself.  The context's own (LzCtx::scratch, counter, tables, pfTables, ev0/ev1) serves every launch that fills
- * the machine, the hashChain levels and decompression, one after the other; a compress launch SMALLER than the machine that
- * arrives on another stream while that one is busy gets one of up to LZ_ARENAS_MAX - 1 more (allocated on first need, 2.6 GiB +
- * tables each; LIZARDGPU_ARENAS=1..4 caps the total, default 4), so that small launches of different streams run side by side
- * on the CUs they leave each other. */
+ * needs one to itself.  The context's own (LzCtx::arena[0], made with the context) serves every launch that fills the machine,
+ * the hashChain levels and decompression, one after the other; a compress launch SMALLER than the machine that arrives on
+ * another stream while that one is busy gets one of up to LZ_ARENAS_MAX - 1 more (allocated on first need, 2.6 GiB + tables
+ * each; LIZARDGPU_ARENAS=1..4 caps the total, default 4), so that small launches of different streams run side by side on the
+ * CUs they leave each other. */
 #define LZ_ARENAS_MAX 4
+#define LZ_ARENA_TABLES 2       /* table classes an arena holds: [0] levels 11/31/22/42 (2^18 u32 slots per wave), [1] levels 20/40/21/41 (64 KiB per wave) */
 typedef struct LzArena {
-    uint8_t* scratch; uint32_t* counter; uint8_t* tables; uint8_t* pfTables;
-    size_t tablesSlots, pfSlots;  /* table slots behind tables / pfTables (fewer than resident waves under a memory budget) */
+    uint8_t* scratch; uint32_t* counter;
+    uint8_t* tables[LZ_ARENA_TABLES];       /* allocated on first use */
+    size_t   tableSlots[LZ_ARENA_TABLES];   /* per-wave slots behind each (fewer than resident waves under a memory budget) */
     hipEvent_t ev0, ev1;        /* around its last launch */
     hipStream_t lastStream;
     int timed;                  /* ev1 was recorded */
@@ -65,22 +67,14 @@ typedef struct LzCtx {
     int   ready;
     int   device;
     int   cus;
-    uint8_t* tables;            /* levels 11/31/22/42, allocated on first use */
-    uint8_t* pfTables;          /* levels 21/41: 64 KiB per resident wave for the waves whose table is not in LDS */
+    LzArena arena[LZ_ARENAS_MAX];   /* [0]: the context's own; [1 .. nArenas): the extra ones */
+    int   nArenas, maxArenas, nextExtra;
+    int      idleLaunches;      /* launches on the context's own arena since an extra arena was last used (they are released after 64) */
     uint8_t* hcSlots;           /* hashChain levels, allocated on first use / when a larger block size arrives */
     size_t   hcMaxBlock, hcNSlots, hcSlotBytes;
     int      hcHasBest;         /* the slots end with the first-search table of levels 16/17/37/38 */
-    size_t   tablesSlots, pfSlots;   /* table slots behind tables / pfTables (fewer than resident waves under a memory budget) */
     size_t   devBytes;          /* device memory this context holds in its large buffers (arenas, tables, work areas, staging): what
                                  * LizardGPU_setMemoryBudget bounds and LizardGPU_memoryInUse reports */
-    int      idleLaunches;      /* launches on the context's own arena since an extra arena was last used (they are released after 64) */
-    uint8_t* scratch;
-    uint32_t* counter;
-    hipEvent_t ev0, ev1;
-    int   timed;
-    hipStream_t lastStream;     /* of the last launch on the context's own arena */
-    LzArena extra[LZ_ARENAS_MAX - 1];
-    int   nExtra, maxArenas, nextExtra;
     hipEvent_t lastEv0, lastEv1;   /* around the most recent launch, whichever arena it used (LizardGPU_lastKernelMs) */
     int   lastSplit;            /* the last compress launch was the producer / consumer form (profile builds: where the records are) */
     int   laneOrderOk;          /* self-check at context creation: lanes of one DS atomic are served in lane order */
