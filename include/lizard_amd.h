@@ -13,7 +13,7 @@
  *   Part 1d  XXH32 / XXH64          lib/xxhash/xxhash.h         (XXH_NAMESPACE=Lizard_, lib/Makefile:52)
  *   Part 2   batch extension (ours): many independent blocks per call, host- or device-resident, several GPUs, decompression
  *   Part 3   the strict frame twins of rounds 2-3 (LizardGPU_compressFrame ...)
- *   Part 3b  whole-frame decompression on the GPU (LizardGPU_decompressFrame ...)
+ *   Part 3b  whole-frame decompression on the GPU (LizardGPU_decompressFrame, LizardGPU_decompressFrame_device ...)
  *
  * Plain C, plain pointers and sizes; no HIP or torch types in any signature (a HIP stream is passed
  * as an opaque void*).
@@ -469,6 +469,48 @@ int LizardGPU_frameIndex(const void* src, size_t srcSize, LizardGPU_frameInfo_t*
  * device before the copy. */
 int LizardGPU_frameDecodeStats(unsigned long long out[4]);
 unsigned long long LizardGPU_frameDecodePackedChunks(void);
+
+/* ---- the same for a frame that already lies in DEVICE memory, decoded into device memory ----
+ * Nothing but a few bytes per record crosses PCIe: the frame is walked on the device (one wave, in segments of 4 096 records,
+ * LIZARDGPU_WALK_RECORDS overrides; the walk of a segment runs while the segment before it is decoded) and every record is decoded
+ * straight to its place in d_dst.  Records behind a short block in the middle of a frame (flushed frames) go through the context's
+ * staging slots and are moved into place on the device. */
+
+#define LIZARDGPU_FRAME_SKIP_CHECKSUM 1u   /* do not verify the content checksum (it is still required to be present) */
+
+/* Decodes the ONE frame that starts at d_src (device memory, srcSize bytes) into d_dst (device memory).  SYNCHRONOUS: the work
+ * is ordered after what `stream` holds at the call, and when the call returns the result is visible to work enqueued on `stream`
+ * afterwards.  Return value, *srcConsumedPtr (a host value, may be NULL) and the decoded bytes are what LizardGPU_decompressFrame
+ * answers for the same frame bytes in host memory, for every input, intact or damaged, and every capacity — including the order of
+ * its refusals: a record chain that is refused outranks a corrupt block or a buffer that is too small.  Nothing outside
+ * d_dst[0..dstCapacity) is written, nothing outside d_src[0..srcSize) is read; the bytes of d_dst behind the returned size are
+ * unspecified.  A skippable frame decodes to 0 bytes.
+ * Content checksum: XXH32 is one serial chain over the whole stream and runs on the HOST.  Unless flags has
+ * LIZARDGPU_FRAME_SKIP_CHECKSUM, the decoded bytes of a frame that carries a checksum are copied to pinned host memory in pieces
+ * and hashed there by the calling thread — a segment's bytes while the next segment decodes, the last or only segment's after its
+ * decode: that costs one D2H crossing and bounds the call by the host's hashing rate.  With
+ * the flag a wrong stored checksum is not noticed; a frame too short to hold its checksum is refused either way.
+ * A LINKED frame with a block that reaches into its history (the reference's linked frames, never this library's) is finished on
+ * the host: the frame is copied to pinned memory, decoded by LizardGPU_decompressFrame and the result copied into d_dst.
+ * No device or a HIP failure is LIZARDGPU_FRAME_ERR_GENERIC (LizardGPU_lastError has the text), never a silent fall-back. */
+size_t LizardGPU_decompressFrame_device(void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize, size_t* srcConsumedPtr,
+                                        unsigned flags, void* stream);
+
+/* LizardGPU_frameIndex for a frame in device memory, walked on the device: d_payloadOffsets / d_recordWords are DEVICE arrays of
+ * maxRecords entries (either may be NULL); info, *nRecords and *frameBytes are host values.  The same return code and values as
+ * LizardGPU_frameIndex for the same bytes.  Synchronous, ordered after what `stream` holds. */
+int LizardGPU_frameIndex_device(const void* d_src, size_t srcSize, LizardGPU_frameInfo_t* info, uint64_t* d_payloadOffsets,
+                                uint32_t* d_recordWords, size_t maxRecords, size_t* nRecords, size_t* frameBytes, void* stream);
+
+/* Since process start, selected device: [0] records decoded straight into the caller's buffer, [1] records that went through
+ * staging and were gathered into place, [2] frames finished on the host because a block needed its history, [3] walk segments
+ * launched.  0 or -LIZARDGPU_ERR_*. */
+int LizardGPU_frameDecodeDeviceStats(unsigned long long out[4]);
+
+/* Records per walk segment in effect (LIZARDGPU_WALK_RECORDS when it holds 1 .. 2^20, else the default), and the maximum block
+ * size of a frame's block size id (0 = the default id; 0 for an id above 7). */
+size_t LizardGPU_frameWalkRecords(void);
+size_t LizardGPU_frameBlockSize(unsigned blockSizeID);
 
 #ifdef __cplusplus
 }

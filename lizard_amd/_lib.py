@@ -87,6 +87,14 @@ def lib():
     L.LizardGPU_frameIndex.restype = c.c_int
     L.LizardGPU_frameDecodeStats.argtypes = [c.c_void_p]; L.LizardGPU_frameDecodeStats.restype = c.c_int
     L.LizardGPU_frameDecodePackedChunks.restype = c.c_ulonglong
+    L.LizardGPU_decompressFrame_device.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_uint, c.c_void_p]
+    L.LizardGPU_decompressFrame_device.restype = c.c_size_t
+    L.LizardGPU_frameIndex_device.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p,
+                                              c.c_void_p]
+    L.LizardGPU_frameIndex_device.restype = c.c_int
+    L.LizardGPU_frameWalkRecords.restype = c.c_size_t
+    L.LizardGPU_frameBlockSize.argtypes = [c.c_uint]; L.LizardGPU_frameBlockSize.restype = c.c_size_t
+    L.LizardGPU_frameDecodeDeviceStats.argtypes = [c.c_void_p]; L.LizardGPU_frameDecodeDeviceStats.restype = c.c_int
     _lib = L
     return L
 

@@ -189,3 +189,73 @@ def decompress_frame(data):
         out.append(dst[:n].tobytes())
         pos += used.value
     return b"".join(out)
+
+
+FRAME_SKIP_CHECKSUM = 1
+_INDEX_GUESS = 1 << 16          # records the first walk of frame_index_device has tables for (16 GiB of output at 256 KiB blocks)
+
+
+def frame_index_device(src):
+    """LizardGPU_frameIndex_device: header fields and record table of the frame at the start of `src`, a contiguous uint8 CUDA
+    tensor, walked on the device on torch's current stream.  The keys of frame_info, plus "offsets" (int64) and "words" (int32
+    view of the LE32 record words: negative = stored raw) as tensors on src's device."""
+    import torch
+    L = _lib.lib()
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+    L.LizardGPU_setDevice(src.device.index or 0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
+    info = _FrameInfo()
+    n, fb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    size = int(src.numel())
+    room = min(_INDEX_GUESS, size // 5 + 1)                    # (a record is 5 bytes at least)
+    while True:                                                # one walk, unless the frame has more records than the guess
+        offsets = torch.empty(room, dtype=torch.int64, device=src.device)
+        words = torch.empty(room, dtype=torch.int32, device=src.device)
+        rc = L.LizardGPU_frameIndex_device(src.data_ptr(), size, ctypes.byref(info), offsets.data_ptr(), words.data_ptr(), room,
+                                           ctypes.byref(n), ctypes.byref(fb), stream)
+        if rc:
+            _lib.check_frame((1 << 64) + rc, "LizardGPU_frameIndex_device")
+        if n.value <= room:
+            break
+        room = n.value
+    offsets, words = offsets[:n.value], words[:n.value]
+    bound = 0
+    if n.value:
+        block = L.LizardGPU_frameBlockSize(info.blockSizeID)
+        bound = int(torch.where(words < 0, words & 0x7FFFFFFF, torch.full_like(words, block)).sum(dtype=torch.int64).item())
+        if info.contentSize and info.contentSize < bound:
+            bound = int(info.contentSize)
+    return {"block_size_id": info.blockSizeID, "independent": bool(info.blockMode), "checksum": bool(info.contentChecksumFlag),
+            "skippable": bool(info.frameType), "content_size": info.contentSize, "n_records": n.value, "frame_bytes": fb.value,
+            "bound": bound, "offsets": offsets, "words": words}
+
+
+def decompress_frame_device(src, dst=None, verify_checksum=True):
+    """Decode the frame(s) in `src`, a contiguous uint8 CUDA tensor, into a uint8 CUDA tensor on the same device
+    (LizardGPU_decompressFrame_device) on torch's current stream: neither the frame nor the decoded bytes cross PCIe, unless
+    verify_checksum asks for the content checksum, which is computed on the host.  Concatenated frames are decoded one after the
+    other, skippable frames contribute nothing.  Without `dst` the output is sized by a walk of every frame (frame_index_device).
+    Returns the decoded bytes (a view of `dst` when given); an error code raises."""
+    import torch
+    L = _lib.lib()
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+    size = int(src.numel())
+    if dst is None:
+        total, pos = 0, 0
+        while pos < size:
+            info = frame_index_device(src[pos:])
+            total += info["bound"]
+            pos += info["frame_bytes"]
+        dst = torch.empty(max(total, 1), dtype=torch.uint8, device=src.device)[:total]
+    assert dst.is_cuda and dst.dtype == torch.uint8 and dst.is_contiguous() and dst.device == src.device
+    L.LizardGPU_setDevice(src.device.index or 0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
+    flags = 0 if verify_checksum else FRAME_SKIP_CHECKSUM
+    cap, pos, out = int(dst.numel()), 0, 0
+    while pos < size:
+        used = ctypes.c_size_t(0)
+        n = _lib.check_frame(L.LizardGPU_decompressFrame_device(dst.data_ptr() + out, cap - out, src.data_ptr() + pos, size - pos,
+                                                                ctypes.byref(used), flags, stream), "LizardGPU_decompressFrame_device")
+        out += n
+        pos += used.value
+    return dst[:out]

@@ -19,6 +19,7 @@
 #include "lizard_gpu_ctx.h"
 #include "lz_kernels.h"   // LzBatch / LzUnBatch, residency knobs, the kernels
 #include "unframe_kernels.h"   // lz_unframe_kernel: the block records of a frame (LizardGPU_decompressFrame)
+#include "unframe_walk.h"      // lz_unframe_walk_kernel: the walk over a frame in device memory (LizardGPU_decompressFrame_device)
 
 namespace {
 
@@ -221,6 +222,8 @@ void ctx_release(Ctx& c)
         memset(&s, 0, sizeof s);
     }
     lzk_combiner_free(&c);
+    if (c.dfTab) (void)hipFree(c.dfTab);
+    c.dfTab = nullptr; c.dfTabCap = 0;
     for (LzArena& x : c.arena) arena_destroy(c, x);             // (every slot: one that was never made, or made half, holds nulls)
     free_hc_slots(c);
     c.nArenas = 0; c.nextExtra = 0; c.lastEv0 = c.lastEv1 = nullptr; c.laneOrderOk = 1; c.ready = 0;
@@ -545,6 +548,46 @@ int launch_unframe(Ctx& c, const void* d_src, const u64* d_payloadOffsets, const
     return enqueue_on(c, own, stream, nullptr, nullptr, [&] { hipLaunchKernelGGL(lz_unframe_kernel, dim3(grid), dim3(64 * LZ_WAVES_DEC), 0, stream, a); });
 }
 
+// The same with the slots inside the caller's buffer (lz_unframe_inplace_kernel).
+int launch_unframe_inplace(Ctx& c, const void* d_src, const u64* d_payloadOffsets, const u32* d_words, size_t nRecords, void* d_dst,
+                           size_t slotBytes, size_t dstRoom, u32* d_outSizes, u32* d_packSizes, hipStream_t stream)
+{
+    if (!d_src || !d_payloadOffsets || !d_words || !d_dst || !d_outSizes || !d_packSizes || nRecords == 0 || nRecords > 0xFFFFFFFFu || slotBytes == 0
+        || dstRoom == 0 || (nRecords - 1) > (dstRoom - 1) / slotBytes) {
+        snprintf(t_err, sizeof t_err, "bad argument (null pointer, zero size or a slot that starts outside the buffer)");
+        return -LIZARDGPU_ERR_ARG;
+    }
+    int rc = ctx_init(c);
+    if (rc) return rc;
+    LzArena& own = c.arena[0];
+    LzUnframeInPlaceBatch a;
+    a.src = (const u8*)d_src; a.payloadOffsets = d_payloadOffsets; a.words = d_words;
+    a.dst = (u8*)d_dst; a.slotBytes = slotBytes; a.dstRoom = dstRoom; a.outSizes = d_outSizes; a.packSizes = d_packSizes; a.nRecords = (u32)nRecords;
+    a.scratch = own.scratch; a.counter = own.counter;
+    u32 grid = (u32)((nRecords + LZ_WAVES_DEC - 1) / LZ_WAVES_DEC);
+    if (grid > (u32)c.cus) grid = (u32)c.cus;
+    c.hostKernelMs = -1.0f;
+    return enqueue_on(c, own, stream, nullptr, nullptr, [&] { hipLaunchKernelGGL(lz_unframe_inplace_kernel, dim3(grid), dim3(64 * LZ_WAVES_DEC), 0, stream, a); });
+}
+
+// One segment of the frame walk (unframe_walk.h): one wave, no arena.
+int launch_walk(Ctx& c, const void* d_src, size_t srcSize, size_t startPos, size_t budget, size_t tableCap, u64* d_offs, u32* d_words,
+                LzWalkResult* d_res, hipStream_t stream)
+{
+    if ((!d_src && srcSize) || !d_res || startPos > srcSize) {
+        snprintf(t_err, sizeof t_err, "bad argument (null pointer or a start behind the end)");
+        return -LIZARDGPU_ERR_ARG;
+    }
+    int rc = ctx_init(c);
+    if (rc) return rc;
+    LzWalkArgs a;
+    a.src = (const u8*)d_src; a.srcSize = srcSize; a.startPos = startPos; a.budget = budget; a.tableCap = tableCap;
+    a.offs = d_offs; a.words = d_words; a.res = d_res;
+    hipLaunchKernelGGL(lz_unframe_walk_kernel, dim3(1), dim3(64), 0, stream, a);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 #include "lizard_shard.h"   // single-process multi-device entry + RCCL size gather (uses Guard / launch above)
@@ -663,6 +706,7 @@ int LizardGPU_trim(void)
                 if (s.h_out) (void)hipHostFree(s.h_out);
                 s.h_in = s.h_out = nullptr; s.h_in_cap = s.h_out_cap = 0;
             }
+            dev_free(c, c.dfTab, c.dfTabCap); c.dfTab = nullptr; c.dfTabCap = 0;
             if (g.c == cpeek) lzk_combiner_free(&c);
         }
     }
@@ -735,6 +779,16 @@ int   lzk_launch_unframe(LzCtx* c, const void* d_src, const uint64_t* d_payloadO
                          size_t slotBytes, uint32_t* d_outSizes, uint32_t* d_packSizes, hipStream_t stream)
 {
     return launch_unframe(*c, d_src, (const u64*)d_payloadOffsets, d_words, nRecords, d_slots, slotBytes, d_outSizes, d_packSizes, stream);
+}
+int   lzk_launch_walk(LzCtx* c, const void* d_src, size_t srcSize, size_t startPos, size_t budget, size_t tableCap, uint64_t* d_offs,
+                      uint32_t* d_words, struct LzWalkResult* d_res, hipStream_t stream)
+{
+    return launch_walk(*c, d_src, srcSize, startPos, budget, tableCap, (u64*)d_offs, d_words, d_res, stream);
+}
+int   lzk_launch_unframe_inplace(LzCtx* c, const void* d_src, const uint64_t* d_payloadOffsets, const uint32_t* d_words, size_t nRecords,
+                                 void* d_dst, size_t slotBytes, size_t dstRoom, uint32_t* d_outSizes, uint32_t* d_packSizes, hipStream_t stream)
+{
+    return launch_unframe_inplace(*c, d_src, (const u64*)d_payloadOffsets, d_words, nRecords, d_dst, slotBytes, dstRoom, d_outSizes, d_packSizes, stream);
 }
 void  lzk_pack_launch(const void* d_in, const void* d_slots, size_t slot, const uint32_t* d_sizes, uint64_t* d_offsets, void* d_packed,
                       uint32_t nb, uint32_t blockSize, uint32_t lastBlockSize, int mode, hipStream_t stream)

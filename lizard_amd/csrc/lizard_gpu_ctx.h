@@ -80,6 +80,11 @@ typedef struct LzCtx {
     int   laneOrderOk;          /* self-check at context creation: lanes of one DS atomic are served in lane order */
     float hostKernelMs;         /* sum over the chunks of the last host-buffer call (< 0: last call was a device call) */
     unsigned long long unframeStats[5];   /* LizardGPU_frameDecodeStats [0..3], [4] = chunks packed on the device; since process start */
+    /* LizardGPU_decompressFrame_device / LizardGPU_frameIndex_device (lizard_unframe_device.c): the record tables, per-record results
+     * and result records of the two walk segments in flight (device, counted in devBytes) and its statistics; its staging slots and
+     * pinned buffers are the stages' */
+    uint8_t* dfTab;     size_t dfTabCap;
+    unsigned long long devFrameStats[4];  /* LizardGPU_frameDecodeDeviceStats; since process start */
     LzStage stage[LZ_STAGES];
     LzCombine comb;
     pthread_mutex_t mu;
@@ -120,6 +125,15 @@ int   lzk_launch_decompress(LzCtx* c, const void* d_src, const uint64_t* d_offse
  * decoded into slot i * slotBytes; d_outSizes[i] = size / 0xFFFFFFFE (needs history) / 0xFFFFFFFF, d_packSizes[i] = valid bytes of the slot */
 int   lzk_launch_unframe(LzCtx* c, const void* d_src, const uint64_t* d_payloadOffsets, const uint32_t* d_words, size_t nRecords, void* d_slots,
                          size_t slotBytes, uint32_t* d_outSizes, uint32_t* d_packSizes, hipStream_t stream);
+/* one segment of the walk over the frame at d_src (unframe_walk.h): from startPos (0 = the header first) over at most `budget`
+ * records; the first tableCap of them go to d_offs / d_words (either may be NULL); *d_res tells how the segment ended */
+struct LzWalkResult;
+int   lzk_launch_walk(LzCtx* c, const void* d_src, size_t srcSize, size_t startPos, size_t budget, size_t tableCap, uint64_t* d_offs,
+                      uint32_t* d_words, struct LzWalkResult* d_res, hipStream_t stream);
+/* lzk_launch_unframe with the slots inside the caller's buffer: record i decodes to d_dst + i * slotBytes, room
+ * min(slotBytes, dstRoom - i * slotBytes); nRecords <= ceil(dstRoom / slotBytes) */
+int   lzk_launch_unframe_inplace(LzCtx* c, const void* d_src, const uint64_t* d_payloadOffsets, const uint32_t* d_words, size_t nRecords,
+                                 void* d_dst, size_t slotBytes, size_t dstRoom, uint32_t* d_outSizes, uint32_t* d_packSizes, hipStream_t stream);
 /* exclusive scan of the record sizes + compaction of the valid bytes into d_packed (lz_pack.h); mode: LZK_PACK_* */
 void  lzk_pack_launch(const void* d_in, const void* d_slots, size_t slot, const uint32_t* d_sizes, uint64_t* d_offsets, void* d_packed,
                       uint32_t nb, uint32_t blockSize, uint32_t lastBlockSize, int mode, hipStream_t stream);

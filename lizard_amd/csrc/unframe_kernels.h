@@ -53,4 +53,35 @@ __global__ __launch_bounds__(64 * LZ_WAVES_DEC) void lz_unframe_kernel(LzUnframe
         lz_converge();
     }
 }
+
+// The same for a frame decoded where it lies (LizardGPU_decompressFrame_device): the slots are positions inside the caller's buffer.
+// Record i goes to dst + i * slotBytes — the place it has when every earlier record fills its block — with room for
+// min(slotBytes, dstRoom - i * slotBytes) bytes: the last slot of an exactly-sized buffer is short.  The host launches only records
+// whose slot starts inside the buffer (nRecords <= ceil(dstRoom / slotBytes)), so nothing outside dst[0..dstRoom) is written.
+struct LzUnframeInPlaceBatch {
+    const u8* src; const u64* payloadOffsets; const u32* words;
+    u8* dst; u64 slotBytes; u64 dstRoom; u32* outSizes; u32* packSizes; u32 nRecords;
+    u8* scratch; u32* counter;
+};
+
+__global__ __launch_bounds__(64 * LZ_WAVES_DEC) void lz_unframe_inplace_kernel(LzUnframeInPlaceBatch a)
+{
+    __shared__ u32 ws[LZ_WAVES_DEC][LZD_WS_WORDS];
+    const u32 wave = lz_uniform(threadIdx.x >> 6);
+    u8* stage = a.scratch + ((u64)blockIdx.x * LZ_MAX_WAVES + wave) * LZ_SCRATCH_BYTES;
+    for (;;) {
+        lz_converge();
+        const u32 b = lz_claim_index(a.counter);
+        if (b >= a.nRecords) break;
+        const u64 at = (u64)b * a.slotBytes;
+        u32 r = LZD_ERR;
+        if (at < a.dstRoom) {
+            u64 room = a.dstRoom - at;
+            if (room > a.slotBytes) room = a.slotBytes;
+            r = lz_unframe_record(a.src + a.payloadOffsets[b], a.words[b], a.dst + at, room > 0x7FFFFFFFull ? 0x7FFFFFFFu : (u32)room, stage, ws[wave]);
+        }
+        if (lz_lane() == 0) { a.outSizes[b] = r; a.packSizes[b] = r >= LZD_NEED_HISTORY ? 0u : r; }
+        lz_converge();
+    }
+}
 #endif
