@@ -49,6 +49,7 @@ static int g_mode = FH_EAGER, g_abort = 1, g_pageable = 0, g_violations;
 static unsigned g_rng = 1u;
 static char g_first[512];
 static unsigned long long g_opsRun;
+static int g_failMalloc;                                                   /* fh_fail_malloc: the n-th hipMalloc from now fails */
 
 static void init_once(void)
 {
@@ -200,6 +201,7 @@ void fh_register_pinned(const void* p, size_t n) { lock(); add_mem((void*)(uintp
 void fh_unregister_pinned(const void* p) { lock(); run_all(); if (!drop_mem(p, MEM_REGISTERED, MEM_REGISTERED)) fail("fh_unregister_pinned(%p): not registered", p); unlock(); }
 void fh_allow_pageable(int on) { lock(); g_pageable += on ? 1 : (g_pageable > 0 ? -1 : 0); unlock(); }      /* (a count: several threads may ask) */
 int  fh_check_dev(const void* p, size_t n, const char* what) { int ok; lock(); ok = dev_ok(p, n, what); unlock(); return ok; }
+void fh_fail_malloc(int nth) { lock(); g_failMalloc = nth; unlock(); }
 unsigned fh_rand(void) { unsigned r; lock(); r = rnd(); unlock(); return r; }
 unsigned long long fh_ops_run(void) { unsigned long long v; lock(); v = g_opsRun; unlock(); return v; }
 void fh_assert_idle(const char* where)
@@ -247,7 +249,13 @@ static hipError_t free_mem(void* p, int kind, const char* name)
     free(p);
     return hipSuccess;
 }
-hipError_t hipMalloc(void** p, size_t n) { return alloc_mem(p, n, MEM_DEV, 0xD5); }
+hipError_t hipMalloc(void** p, size_t n)
+{
+    int refuse;
+    lock(); refuse = g_failMalloc && !--g_failMalloc; unlock();
+    if (refuse) { *p = NULL; return hipErrorOutOfMemory; }
+    return alloc_mem(p, n, MEM_DEV, 0xD5);
+}
 hipError_t hipFree(void* p) { return free_mem(p, MEM_DEV, "hipFree"); }
 hipError_t hipHostMalloc(void** p, size_t n, unsigned flags) { (void)flags; return alloc_mem(p, n, MEM_PINNED, 0xB6); }
 hipError_t hipHostFree(void* p) { return free_mem(p, MEM_PINNED, "hipHostFree"); }

@@ -26,6 +26,7 @@ hipError_t fh_enqueue_kernel(hipStream_t st, void (*fn)(void*), const void* arg,
 int  fh_check_dev(const void* p, size_t n, const char* what);
 void fh_assert_idle(const char* where);                       /* every stream's queue is empty, or a check failure */
 unsigned fh_rand(void);
+void fh_fail_malloc(int nth);                                  /* the nth hipMalloc from now answers hipErrorOutOfMemory, once (0: none) */
 unsigned long long fh_ops_run(void);
 #ifdef __cplusplus
 }

@@ -6,7 +6,11 @@
  * oracle as the compress kernels, a plain model of lz_scan_kernel + lz_gather_kernel.  lizard_frame_host.c, lizard_decode_host.c and
  * lizard_xxhash.c are linked as they are.  Every "kernel" checks that what it touches lies in live device memory.
  *   library : gcc -shared -Wl,-Bsymbolic ... (tests/test_pipeline_fake.py drives it through ctypes)
- *   program : -DPIPELINE_FAKE_MAIN, for the sanitizer builds:  pipeline_fake core | threads [n] [rounds]        exit 0 = all good */
+ * lizard_unframe_device.c (LizardGPU_decompressFrame_device / LizardGPU_frameIndex_device: walk, decode and checksum streams, two table
+ * sets, the in-place pass and the staging pass, the device-side gather) is a third unit on the same fake: its walk is the real
+ * lz_unframe_walk body on the emulator, its in-place launch a restatement of lz_unframe_inplace_kernel's slot rule.
+ *   program : -DPIPELINE_FAKE_MAIN, for the sanitizer builds:  pipeline_fake core | threads [n] [rounds] | devcore | devthreads [n] [rounds]
+ *             exit 0 = all good */
 #define _GNU_SOURCE
 #include <pthread.h>
 #include <stdio.h>
@@ -17,17 +21,25 @@
 #include "../lizard_amd/csrc/lizard_pipeline_host.c"      /* units under test, compiled into this harness */
 #undef LZ_HIP
 #include "../lizard_amd/csrc/lizard_unframe_host.c"
+#undef LZ_HIP
+#include "../lizard_amd/csrc/lizard_unframe_device.c"     /* (its statics are v_* / LZV_*, the host twin's uf_* / LZU_*) */
 #include "fake_hip.h"
 #include "lizard_oracle.h"
 
 unsigned emul_unframe_record(const void* payload, unsigned size, unsigned word, void* slot, unsigned cap, unsigned seed);
 unsigned emul_decompress_block_raw(const void* src, unsigned n, void* dst, unsigned cap, unsigned seed);
+void emul_walk_segment(const void* src, unsigned long long srcSize, unsigned long long startPos, unsigned long long budget,
+                       unsigned long long tableCap, unsigned long long* offs, unsigned* words, void* res, unsigned seed);
 
 /* ---- the shims of lizard_gpu_ctx.h ---- */
 static LzCtx g_c;
 static pthread_once_t g_ctxOnce = PTHREAD_ONCE_INIT;
 static __thread char t_err[LZK_ERR_BYTES];
 static int g_degraded;
+/* pf_refuse_launch: the n-th launch of that kind from now answers -LIZARDGPU_ERR_HIP, once, and enqueues nothing */
+enum { PF_WALK, PF_INPLACE, PF_UNFRAME, PF_KINDS };
+static int g_refuse[PF_KINDS];
+static int refused(int kind) { return g_refuse[kind] && !--g_refuse[kind]; }
 static void ctx_once(void) { pthread_mutex_init(&g_c.mu, NULL); pthread_mutex_init(&g_c.comb.mu, NULL); pthread_cond_init(&g_c.comb.cv, NULL); }
 void  lzk_guard_acquire(LzGuard* g) { pthread_once(&g_ctxOnce, ctx_once); pthread_mutex_lock(&g_c.mu); t_err[0] = 0; g->c = &g_c; g->saved = -1; g->rc = 0; }
 /* the product drains what it left in flight before it gives the context back, also after an error or a give-up */
@@ -86,12 +98,73 @@ int lzk_launch_unframe(LzCtx* c, const void* d_src, const uint64_t* d_payloadOff
                        size_t slotBytes, uint32_t* d_outSizes, uint32_t* d_packSizes, hipStream_t stream)
 {
     UnframeK k;
-    (void)c;
     if (!d_src || !d_payloadOffsets || !d_words || !d_slots || !d_outSizes || !d_packSizes || nRecords == 0 || slotBytes == 0) return -LIZARDGPU_ERR_ARG;
+    if (refused(PF_UNFRAME)) { snprintf(t_err, sizeof t_err, "lzk_launch_unframe: refused by the test"); return -LIZARDGPU_ERR_HIP; }
     k.src = (const uint8_t*)d_src; k.offs = d_payloadOffsets; k.words = d_words; k.n = nRecords; k.slots = (uint8_t*)d_slots; k.slotBytes = slotBytes;
     k.outSizes = d_outSizes; k.packSizes = d_packSizes;
     c->hostKernelMs = -1.0f;
     return fh_enqueue_kernel(stream, unframe_kernel, &k, sizeof k) == hipSuccess ? 0 : -LIZARDGPU_ERR_HIP;
+}
+
+/* lz_unframe_inplace_kernel: the slots are places inside the caller's buffer, the last one as short as the room that is left */
+typedef struct { const uint8_t* src; const uint64_t* offs; const uint32_t* words; size_t n; uint8_t* dst; size_t slotBytes, dstRoom; uint32_t *outSizes, *packSizes; } InplaceK;
+static void inplace_kernel(void* a)
+{
+    const InplaceK* k = (const InplaceK*)a;
+    uint32_t* order = (uint32_t*)malloc(k->n * sizeof *order);
+    size_t i;
+    if (!fh_check_dev(k->offs, 8 * k->n, "inplace: payload offsets") || !fh_check_dev(k->words, 4 * k->n, "inplace: words")
+        || !fh_check_dev(k->outSizes, 4 * k->n, "inplace: outSizes") || !fh_check_dev(k->packSizes, 4 * k->n, "inplace: packSizes")
+        || !fh_check_dev(k->dst, k->dstRoom, "inplace: dst[0..dstRoom)")) { free(order); return; }
+    shuffled(order, k->n);
+    for (i = 0; i < k->n; i++) {
+        const uint32_t b = order[i], word = k->words[b], size = word & 0x7FFFFFFFu;
+        const size_t at = (size_t)b * k->slotBytes;
+        uint32_t r = 0xFFFFFFFFu;
+        if (at < k->dstRoom) {
+            size_t room = k->dstRoom - at;
+            if (room > k->slotBytes) room = k->slotBytes;
+            if (room > 0x7FFFFFFFull) room = 0x7FFFFFFFull;
+            if (size && size <= room && !fh_check_dev(k->src + k->offs[b], size, "inplace: a record's payload")) continue;
+            r = emul_unframe_record(k->src + k->offs[b], size, word, k->dst + at, (uint32_t)room, fh_rand() | 1u);
+        }
+        k->outSizes[b] = r; k->packSizes[b] = r >= 0xFFFFFFFEu ? 0u : r;
+    }
+    free(order);
+}
+int lzk_launch_unframe_inplace(LzCtx* c, const void* d_src, const uint64_t* d_payloadOffsets, const uint32_t* d_words, size_t nRecords,
+                               void* d_dst, size_t slotBytes, size_t dstRoom, uint32_t* d_outSizes, uint32_t* d_packSizes, hipStream_t stream)
+{
+    InplaceK k;
+    if (!d_src || !d_payloadOffsets || !d_words || !d_dst || !d_outSizes || !d_packSizes || nRecords == 0 || nRecords > 0xFFFFFFFFu || slotBytes == 0
+        || dstRoom == 0 || (nRecords - 1) > (dstRoom - 1) / slotBytes) { snprintf(t_err, sizeof t_err, "lzk_launch_unframe_inplace: bad argument"); return -LIZARDGPU_ERR_ARG; }
+    if (refused(PF_INPLACE)) { snprintf(t_err, sizeof t_err, "lzk_launch_unframe_inplace: refused by the test"); return -LIZARDGPU_ERR_HIP; }
+    k.src = (const uint8_t*)d_src; k.offs = d_payloadOffsets; k.words = d_words; k.n = nRecords; k.dst = (uint8_t*)d_dst; k.slotBytes = slotBytes;
+    k.dstRoom = dstRoom; k.outSizes = d_outSizes; k.packSizes = d_packSizes;
+    c->hostKernelMs = -1.0f;
+    return fh_enqueue_kernel(stream, inplace_kernel, &k, sizeof k) == hipSuccess ? 0 : -LIZARDGPU_ERR_HIP;
+}
+
+/* lz_unframe_walk_kernel: the real walk on the emulator, one wave */
+typedef struct { const uint8_t* src; size_t srcSize, startPos, budget, tableCap; uint64_t* offs; uint32_t* words; LzWalkResult* res; } WalkK;
+static void walk_kernel(void* a)
+{
+    const WalkK* k = (const WalkK*)a;
+    if ((k->srcSize && !fh_check_dev(k->src, k->srcSize, "walk: src[0..srcSize)")) || !fh_check_dev(k->res, sizeof *k->res, "walk: result record")
+        || (k->offs && k->tableCap && !fh_check_dev(k->offs, 8 * k->tableCap, "walk: offset table"))
+        || (k->words && k->tableCap && !fh_check_dev(k->words, 4 * k->tableCap, "walk: word table"))) return;
+    emul_walk_segment(k->src, k->srcSize, k->startPos, k->budget, k->tableCap, (unsigned long long*)k->offs, k->words, k->res, fh_rand() | 1u);
+}
+int lzk_launch_walk(LzCtx* c, const void* d_src, size_t srcSize, size_t startPos, size_t budget, size_t tableCap, uint64_t* d_offs,
+                    uint32_t* d_words, struct LzWalkResult* d_res, hipStream_t stream)
+{
+    WalkK k;
+    (void)c;
+    if ((!d_src && srcSize) || !d_res || startPos > srcSize) { snprintf(t_err, sizeof t_err, "lzk_launch_walk: bad argument"); return -LIZARDGPU_ERR_ARG; }
+    if (refused(PF_WALK)) { snprintf(t_err, sizeof t_err, "lzk_launch_walk: refused by the test"); return -LIZARDGPU_ERR_HIP; }
+    k.src = (const uint8_t*)d_src; k.srcSize = srcSize; k.startPos = startPos; k.budget = budget; k.tableCap = tableCap; k.offs = d_offs; k.words = d_words;
+    k.res = d_res;
+    return fh_enqueue_kernel(stream, walk_kernel, &k, sizeof k) == hipSuccess ? 0 : -LIZARDGPU_ERR_HIP;
 }
 
 /* lz_decompress_kernel */
@@ -199,6 +272,7 @@ void lzk_pack_launch(const void* d_in, const void* d_slots, size_t slot, const u
 
 /* ---- controls for the tests ---- */
 void pf_set_chunk_bytes(size_t n) { LzGuard g; lzk_guard_acquire(&g); g_chunk_bytes = n; lzk_guard_release(&g); }
+void pf_refuse_launch(int kind, int nth) { LzGuard g; lzk_guard_acquire(&g); if (kind >= 0 && kind < PF_KINDS) g_refuse[kind] = nth; lzk_guard_release(&g); }
 int  pf_degraded(void) { return __atomic_load_n(&g_degraded, __ATOMIC_RELAXED); }
 /* what LizardGPU_shutdown does to the stages: the next call allocates (poisoned) buffers afresh */
 void pf_shutdown(void)
@@ -221,6 +295,7 @@ void pf_shutdown(void)
         (void)hipStreamDestroy(s->stream);
         memset(s, 0, sizeof *s);
     }
+    if (g_c.dfTab) { (void)hipFree(g_c.dfTab); g_c.dfTab = NULL; g_c.dfTabCap = 0; }
     g_c.ready = 0; g_c.devBytes = 0;
     lzk_guard_release(&g);
 }
@@ -389,11 +464,126 @@ static int threads(int n, int rounds, int big)
     printf("pipeline_fake threads: %d threads x %d rounds, %d bad, %llu ops\n", n, rounds, bad, fh_ops_run());
     return bad ? 1 : 0;
 }
+
+/* ---- LizardGPU_decompressFrame_device: fake device buffers with canary margins, uploaded on a caller's stream that is not waited for ---- */
+#define DV_G 4096
+static hipStream_t g_user;
+static pthread_mutex_t g_userMu = PTHREAD_MUTEX_INITIALIZER;      /* one caller's stream for all threads: the enqueues of a call stay together */
+static int g_syncUpload;        /* the thread test: another thread may release the context meanwhile, and that asserts that ALL queues are empty */
+static int dev_decode(const Frame* f, size_t cap, unsigned flags, size_t wantResult, int compare)
+{
+    uint8_t *dsrc = NULL, *ddst = NULL, *hsrc = NULL, *hdst = NULL;
+    const size_t sn = f->bytes + 2 * DV_G, dn = cap + 2 * DV_G;
+    size_t used = 1, r, i;
+    int bad = 0;
+    CHECK(hipMalloc((void**)&dsrc, sn) == hipSuccess && hipMalloc((void**)&ddst, dn) == hipSuccess
+          && hipHostMalloc((void**)&hsrc, sn, 0) == hipSuccess && hipHostMalloc((void**)&hdst, dn, 0) == hipSuccess, "allocation");
+    memset(hsrc, 0x5A, sn); memcpy(hsrc + DV_G, f->frame, f->bytes); memset(hdst, 0xC3, dn);
+    pthread_mutex_lock(&g_userMu);
+    if (!g_user) hipStreamCreateWithFlags(&g_user, hipStreamNonBlocking);
+    if (g_syncUpload) { hipMemcpy(dsrc, hsrc, sn, hipMemcpyHostToDevice); hipMemcpy(ddst, hdst, dn, hipMemcpyHostToDevice); }
+    else { hipMemcpyAsync(dsrc, hsrc, sn, hipMemcpyHostToDevice, g_user); hipMemcpyAsync(ddst, hdst, dn, hipMemcpyHostToDevice, g_user); }
+    r = LizardGPU_decompressFrame_device(ddst + DV_G, cap, dsrc + DV_G, f->bytes, &used, flags, g_user);
+    pthread_mutex_unlock(&g_userMu);
+    memset(hdst, 0, dn);
+    hipMemcpy(hdst, ddst, dn, hipMemcpyDeviceToHost);
+    for (i = 0; i < DV_G; i++) bad |= hdst[i] != 0xC3 || hdst[DV_G + cap + i] != 0xC3;
+    if (!bad && (compare == 2 ? !LizardF_isError(r) : r != wantResult)) bad = 2;    /* compare 2: any refusal */
+    if (!bad && !LizardF_isError(r) && (used != f->bytes || (compare == 1 && memcmp(hdst + DV_G, f->plain, r)))) bad = 3;
+    if (!bad && LizardF_isError(r) && used != 0) bad = 4;
+    hipFree(dsrc); hipFree(ddst); hipHostFree(hsrc); hipHostFree(hdst);
+    CHECK(!bad, "decompressFrame_device: %s (result %zu, wanted %zu, consumed %zu of %zu, capacity %zu): %s",
+          bad == 1 ? "a canary margin of d_dst changed" : bad == 2 ? "unexpected result" : bad == 3 ? "wrong bytes or consumed count" : "consumed set on an error",
+          r, wantResult, used, f->bytes, cap, LizardGPU_lastError());
+    return 0;
+}
+static int dev_check(const Frame* f)
+{
+    if (dev_decode(f, f->n, 0, f->n, 1)) return 1;
+    if (dev_decode(f, f->n + 77, 1u, f->n, 1)) return 1;
+    return dev_decode(f, f->n - 1, 0, FERR(dstMaxSize_tooSmall), 0);
+}
+static int devcore(void)
+{
+    static const struct { int mode; unsigned seed; } sched[] = { { FH_EAGER, 1 }, { FH_LAZY, 1 }, { FH_RANDOM, 11 }, { FH_RANDOM, 12 }, { FH_RANDOM, 13 } };
+    static const char* const budget[] = { NULL, "1", "2", "3", "1" };
+    uint8_t* out;
+    size_t s;
+    int f;
+    setup(4 * 131072 + 4321);
+    out = (uint8_t*)malloc(g_n + 64);
+    for (s = 0; s < sizeof sched / sizeof sched[0]; s++) {
+        Frame bad = g_frames[0], cut = g_frames[0];
+        fh_set_schedule(sched[s].mode, sched[s].seed);
+        pf_set_chunk_bytes(s & 1 ? (size_t)1 << 20 : (size_t)256 << 10);
+        if (budget[s]) setenv("LIZARDGPU_WALK_RECORDS", budget[s], 1); else unsetenv("LIZARDGPU_WALK_RECORDS");
+        if (s == 1) pf_shutdown();
+        for (f = 0; f < g_nFrames; f++)
+            if (dev_check(&g_frames[f])) { fprintf(stderr, "  (frame %d, schedule %d seed %u)\n", f, sched[s].mode, sched[s].seed); return 1; }
+        /* capacity edges: a slot border with records to come, inside a slot, nothing */
+        if (dev_decode(&g_frames[0], 2 * 131072, 0, FERR(dstMaxSize_tooSmall), 0) || dev_decode(&g_frames[0], 3 * 131072 + 100, 0, FERR(dstMaxSize_tooSmall), 0)
+            || dev_decode(&g_frames[0], 0, 0, FERR(dstMaxSize_tooSmall), 0)) return 1;
+        /* a damaged record, a frame cut inside its checksum, a stored checksum that is wrong (and skipped), a launch that is refused */
+        bad.frame = (uint8_t*)malloc(bad.bytes); memcpy(bad.frame, g_frames[0].frame, bad.bytes);
+        memset(bad.frame + bad.bytes / 2, 0xFF, 40);
+        if (dev_decode(&bad, g_n, 0, 0, 2)) return 1;
+        memcpy(bad.frame, g_frames[0].frame, bad.bytes); bad.frame[bad.bytes - 1] ^= 1;
+        if (dev_decode(&bad, g_n, 0, FERR(contentChecksum_invalid), 0) || dev_decode(&bad, g_n, 1u, g_n, 1)) return 1;
+        free(bad.frame);
+        cut.bytes -= 2;
+        if (dev_decode(&cut, g_n, 0, FERR(GENERIC), 0)) return 1;
+        pf_refuse_launch((int)(s & 1), s ? 2 : 1);           /* the walk or the in-place launch, of the first or the second segment */
+        if (dev_decode(&g_frames[2], g_n, 0, FERR(GENERIC), 0)) return 1;
+        if (dev_check(&g_frames[2]) || decode_check(&g_frames[1], (int)(s & 1), out)) return 1;
+    }
+    unsetenv("LIZARDGPU_WALK_RECORDS");
+    free(out);
+    printf("pipeline_fake devcore: ok, %llu ops\n", fh_ops_run());
+    return 0;
+}
+static void* dev_worker(void* a)
+{
+    Worker* w = (Worker*)a;
+    uint8_t* out = (uint8_t*)malloc(g_n + (size_t)lzo_compress_bound(1 << 17) + 64);
+    unsigned r = 977u * (unsigned)(w->id + 1);
+    int i;
+    for (i = 0; i < w->rounds && !w->bad; i++) {
+        const Frame* f;
+        r = r * 1664525u + 1013904223u;
+        f = &g_frames[(r >> 12) % (unsigned)g_nFrames];
+        switch ((r >> 8) % 4u) {
+        case 0: w->bad |= decode_check(f, (int)((r >> 16) & 1u), out); break;
+        case 1: w->bad |= compress_check(g_data, g_n / 2, 131072, 10, out); break;
+        default: w->bad |= dev_decode(f, f->n + ((r >> 17) & 1u ? 77 : 0), (r >> 18) & 1u, f->n, 1); break;
+        }
+    }
+    free(out);
+    return NULL;
+}
+static int devthreads(int n, int rounds)
+{
+    pthread_t th[64], wd;
+    Worker w[64];
+    int i, bad = 0;
+    if (n > 64) return 2;
+    setup(3 * 131072 + 99);
+    setenv("LIZARDGPU_WALK_RECORDS", "2", 1);                 /* (before the threads start: the environment is only read from then on) */
+    fh_set_schedule(FH_RANDOM, 2424);
+    g_syncUpload = 1;
+    hipStreamCreateWithFlags(&g_user, hipStreamNonBlocking);
+    pthread_create(&wd, NULL, watchdog, NULL); pthread_detach(wd);
+    for (i = 0; i < n; i++) { w[i].id = i; w[i].rounds = rounds; w[i].bad = 0; pthread_create(&th[i], NULL, dev_worker, &w[i]); }
+    for (i = 0; i < n; i++) { pthread_join(th[i], NULL); bad += w[i].bad; }
+    printf("pipeline_fake devthreads: %d threads x %d rounds, %d bad, %llu ops\n", n, rounds, bad, fh_ops_run());
+    return bad ? 1 : 0;
+}
 int main(int argc, char** argv)
 {
     if (argc > 1 && !strcmp(argv[1], "core")) return core();
+    if (argc > 1 && !strcmp(argv[1], "devcore")) return devcore();
+    if (argc > 1 && !strcmp(argv[1], "devthreads")) return devthreads(argc > 2 ? atoi(argv[2]) : 6, argc > 3 ? atoi(argv[3]) : 3);
     if (argc > 1 && !strcmp(argv[1], "threads")) return threads(argc > 2 ? atoi(argv[2]) : 8, argc > 3 ? atoi(argv[3]) : 6, argc > 4 ? atoi(argv[4]) : 1);
-    fprintf(stderr, "usage: pipeline_fake core | threads [n] [rounds] [big]\n");
+    fprintf(stderr, "usage: pipeline_fake core | threads [n] [rounds] [big] | devcore | devthreads [n] [rounds]\n");
     return 2;
 }
 #endif

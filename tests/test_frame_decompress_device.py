@@ -239,6 +239,50 @@ def test_content_checksum_and_the_skip_flag():
     assert device_only(bad, len(plain), SKIP_CHECKSUM) == (0, len(frame), plain)
 
 
+def big_checksummed_frame():
+    """2 x 32 MiB + 12345 bytes, 256 KiB blocks, content checksum: three pieces of the checksum pass, the last one odd."""
+    data = util.datagen(2 * (32 << 20) + 12345, 0.5, 0.0, 29)
+    frame = fd.make_frame(data, 10, 2, 1, 0, 1)
+    assert frame[4] & 4 and fi.index(frame)[4] == 257
+    return data, frame
+
+
+def run_checksum_pieces():
+    data, frame = big_checksummed_frame()
+    assert both(frame, len(data)) == (0, len(frame), data)
+    bad = frame[:-1] + bytes([frame[-1] ^ 0x40])
+    assert both(bad, len(data))[0] == E_CONTENT_CRC
+    assert device_only(bad, len(data), SKIP_CHECKSUM) == (0, len(frame), data)
+
+
+def test_content_checksum_in_three_pieces():
+    """The D2H / XXH32 loop of the checksum pass with more than one piece at the product's piece size (32 MiB): piece i + 1 is copied
+    into the other pinned buffer while piece i is hashed."""
+    run_checksum_pieces()
+
+
+PIECES_CHILD = r"""
+import sys, os
+import torch
+assert torch.cuda.is_available()
+sys.path.insert(0, os.path.join(%r, "tests"))
+import test_frame_decompress_device as t
+s0 = t.dstats()
+t.run_checksum_pieces()
+d = t.grown(s0)
+assert d[3] == 3 * (257 // 64 + 1) and d[2] == 0, d             # 64 records per segment: 16 MiB of every segment are hashed while the next decodes
+print("ok")
+"""
+
+
+def test_content_checksum_pieces_across_segments():
+    """The same frame with LIZARDGPU_WALK_RECORDS=64 in a fresh child process: five segments, the pieces of a segment are copied and
+    hashed while the next segment decodes."""
+    env = dict(os.environ, LIZARDGPU_WALK_RECORDS="64")
+    r = subprocess.run([sys.executable, "-c", PIECES_CHILD % util.ROOT], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-3000:] + r.stderr[-3000:]
+
+
 def device_index(frame, max_records=None):
     """fi.index through LizardGPU_frameIndex_device: (rc, info, offsets, words, nRecords, frameBytes)."""
     import torch

@@ -316,6 +316,18 @@ def test_lds_atomics_are_served_in_lane_order():
     assert r.returncode == 0 and "violations: 0 " in r.stdout, r.stdout + r.stderr
 
 
+def test_pack_kernels_match_a_sequential_model():
+    """lz_scan_kernel and lz_gather_kernel (lz_pack.h) alone, tests/pack_kernels.hip: offsets and every packed byte against a plain
+    host model, canaries around both.  The scan above 1024 blocks (per-thread stretch, clamped threads) and with a total above 2^32;
+    the gather at lengths 0 / 1 / 15 / 16 / 17 / 31 / 32 / 33 / 4095 / 4096 / 4097 with odd slot strides; the frame mode's
+    stored-raw rule at cs = 0, 1, n - 2, n - 1, n, n + 5 with last blocks of 1, 2 and 4099 bytes.  About 150 cases in one process."""
+    import subprocess
+    exe = os.path.join(os.path.dirname(os.path.abspath(__file__)), "pack_kernels")
+    assert os.path.exists(exe), "run __graft_entry__.build() first"
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and " mismatches: 0" in r.stdout and not r.stdout.startswith("cases: 0 "), r.stdout + r.stderr
+
+
 def test_lane_order_self_check_refuses_dependent_levels():
     """The library checks the lane-order property itself when a device's context is created; a device that fails is refused
     the levels whose kernels depend on it (10/30, hashChain) with a loud error, the others keep working.  The failure branch

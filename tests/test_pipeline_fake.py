@@ -42,7 +42,8 @@ atexit.register(shutil.rmtree, _dir, True)
 @functools.lru_cache(maxsize=None)
 def built(kind):
     """'lib': the harness as a shared library for ctypes; 'asan' / 'tsan': as a program with that sanitizer.  The emulator's objects
-    are built plain in every form (its lanes switch stacks by hand, which the sanitizers' instrumentation does not follow)."""
+    are built plain in every form (its lanes switch stacks by hand, which the sanitizers' instrumentation does not follow).
+    lizard_unframe_device.c (tests/test_pipeline_fake_device.py) is compiled in with a small odd piece size for its checksum pass."""
     util.oracle()
     objs = []
     for src in (os.path.join(HERE, "pipeline_fake_emul.cpp"), os.path.join(HERE, "emul", "simt.cpp")):
@@ -54,7 +55,7 @@ def built(kind):
     flags = {"lib": ["-shared", "-Wl,-Bsymbolic"], "asan": ["-DPIPELINE_FAKE_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
              "tsan": ["-DPIPELINE_FAKE_MAIN", "-fsanitize=thread"]}[kind]
     out = os.path.join(_dir, "libpipeline_fake.so" if kind == "lib" else "pipeline_fake_" + kind)
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu99", "-fPIC", "-Wall", "-Wextra", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+    subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu99", "-fPIC", "-Wall", "-Wextra", "-D__HIP_PLATFORM_AMD__", "-DLZV_HASH_PIECE=40961", "-I/opt/rocm/include",
                            "-I" + os.path.join(util.ROOT, "include"), "-I" + util.ORACLE_DIR, "-I" + HERE] + flags
                           + [os.path.join(HERE, "pipeline_fake.c"), os.path.join(HERE, "fake_hip.c")]
                           + [os.path.join(CSRC, f) for f in ("lizard_frame_host.c", "lizard_decode_host.c", "lizard_xxhash.c")] + objs
