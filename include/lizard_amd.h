@@ -413,6 +413,31 @@ size_t LizardGPU_compressFrameBound(size_t srcSize, const LizardGPU_framePrefs_t
 size_t LizardGPU_compressFrame(void* dstBuffer, size_t dstMaxSize, const void* srcBuffer, size_t srcSize,
                                const LizardGPU_framePrefs_t* preferencesPtr);
 
+/* ---- the same frame for data that already lies in DEVICE memory, written into device memory ----
+ * d_src (srcSize bytes) and d_dst (dstCapacity bytes) are device pointers.  The call answers exactly what LizardGPU_compressFrame
+ * answers for the same source bytes, preferences and capacity: the same return value (a size or an error code) and the same frame
+ * bytes — the refusals above and maxBlockSize_invalid, dstMaxSize_tooSmall below LizardGPU_compressFrameBound, the level clamp, the
+ * block size id shrunk to the input, contentSize != 0 meaning "write srcSize", srcSize == 0.  Like its twin it answers
+ * dstMaxSize_tooSmall for the one frame that can exceed a buffer of exactly the bound: a 1-byte last block (a 10-byte record where the
+ * bound counted 5) behind blocks that were all stored raw, under a header that carries the content size.
+ * SYNCHRONOUS, like LizardGPU_decompressFrame_device: the work is ordered after what `stream` holds at the call, and when the call
+ * returns the frame is visible to work enqueued on `stream` afterwards.  Nothing outside d_dst[0..dstCapacity) is written, nothing
+ * outside d_src[0..srcSize) is read; the bytes of d_dst behind the returned size are unspecified, and so is d_dst after an error
+ * (below the bound it is left untouched).
+ * The input is compressed in chunks of whole blocks (LIZARDGPU_CHUNK_MB; LIZARDGPU_FRAME_CHUNK_BLOCKS = 1 .. 2^20 overrides the blocks
+ * per chunk, read at every call) into the context's staging slots, and the block records are moved to their place in d_dst on the
+ * device; where a chunk's records start is kept in device memory, so all chunks are enqueued without a host round trip.  Without a
+ * content checksum no payload byte crosses PCIe in either direction.  With one, XXH32 runs on the HOST: the source is copied to
+ * pinned memory once, in pieces, and hashed by the calling thread while the device compresses — the call is then bounded by one host
+ * thread's hashing rate.
+ * No device or a HIP failure is LIZARDGPU_FRAME_ERR_GENERIC (LizardGPU_lastError has the text): never a host fall-back, never blocks
+ * stored raw instead. */
+size_t LizardGPU_compressFrame_device(void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize,
+                                      const LizardGPU_framePrefs_t* preferencesPtr, void* stream);
+/* Since process start, selected device: [0] blocks whose compressed form went into a frame, [1] blocks stored raw, [2] chunks
+ * launched, [3] source bytes copied to the host for the checksum.  0 or -LIZARDGPU_ERR_*. */
+int    LizardGPU_frameCompressDeviceStats(unsigned long long out[4]);
+
 /* Streaming form.  LizardGPU_cctx_t replaces LizardF_compressionContext_t (lib/lizard_frame.h:145); the functions
  * replace LizardF_createCompressionContext / _freeCompressionContext (:157-158, int result: 0 or -LIZARDGPU_FRAME_ERR_*),
  * LizardF_compressBegin (:169), LizardF_compressBound (:178), LizardF_compressUpdate (:190), LizardF_flush (:202) and

@@ -95,6 +95,9 @@ def lib():
     L.LizardGPU_frameWalkRecords.restype = c.c_size_t
     L.LizardGPU_frameBlockSize.argtypes = [c.c_uint]; L.LizardGPU_frameBlockSize.restype = c.c_size_t
     L.LizardGPU_frameDecodeDeviceStats.argtypes = [c.c_void_p]; L.LizardGPU_frameDecodeDeviceStats.restype = c.c_int
+    L.LizardGPU_compressFrame_device.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
+    L.LizardGPU_compressFrame_device.restype = c.c_size_t
+    L.LizardGPU_frameCompressDeviceStats.argtypes = [c.c_void_p]; L.LizardGPU_frameCompressDeviceStats.restype = c.c_int
     _lib = L
     return L
 

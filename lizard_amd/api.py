@@ -158,6 +158,32 @@ def compress_frame(data, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksum=Fals
     return out[:n].tobytes()
 
 
+def compress_frame_device(src, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksum=False, content_size=False, dst=None):
+    """One Lizard frame for `src`, a contiguous uint8 CUDA tensor, written into a uint8 CUDA tensor on the same device
+    (LizardGPU_compressFrame_device) on torch's current stream: the bytes LizardGPU_compressFrame writes for the same input.  No
+    payload crosses PCIe unless `checksum` asks for the content checksum, which is computed on the host.  Without `dst` the
+    output has LizardGPU_compressFrameBound bytes.  Returns (dst, n): the frame is dst[:n]; an error code raises."""
+    import torch
+    L = _lib.lib()
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+    size = int(src.numel())
+    p = _FramePrefs()
+    p.frameInfo.blockSizeID = block_size_id
+    p.frameInfo.blockMode = 1
+    p.frameInfo.contentChecksumFlag = 1 if checksum else 0
+    p.frameInfo.contentSize = size if content_size else 0
+    p.compressionLevel = level
+    if dst is None:
+        cap = _lib.check_frame(L.LizardGPU_compressFrameBound(size, ctypes.byref(p)), "LizardGPU_compressFrameBound")
+        dst = torch.empty(cap, dtype=torch.uint8, device=src.device)
+    assert dst.is_cuda and dst.dtype == torch.uint8 and dst.is_contiguous() and dst.device == src.device
+    L.LizardGPU_setDevice(src.device.index or 0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
+    n = _lib.check_frame(L.LizardGPU_compressFrame_device(dst.data_ptr(), int(dst.numel()), src.data_ptr(), size, ctypes.byref(p), stream),
+                         "LizardGPU_compressFrame_device")
+    return dst, n
+
+
 def frame_info(data):
     """Header fields and record table of the frame at the start of `data` (host code, no GPU): a dict with block_size_id,
     independent, checksum, skippable, content_size, n_records, frame_bytes, bound."""

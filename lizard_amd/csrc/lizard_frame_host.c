@@ -149,6 +149,25 @@ size_t LizardF_compressBound(size_t srcSize, const LizardF_preferences_t* prefsP
     }
 }
 
+/* the frame header of lizard_frame.c:403-424 (blockSizeID already resolved), at most LZF_MAX_HEADER bytes: its size */
+static size_t write_header(uint8_t* dst, const LizardF_frameInfo_t* fi)
+{
+    uint8_t* const start = dst;
+    wr32le(dst, LZF_MAGIC); dst += 4;
+    {
+        uint8_t* const headerStart = dst;
+        *dst++ = (uint8_t)((1u << 6) + ((fi->blockMode & 1u) << 5) + ((fi->contentChecksumFlag & 1u) << 2) + ((fi->contentSize > 0) << 3));
+        *dst++ = (uint8_t)((fi->blockSizeID & 7u) << 4);
+        if (fi->contentSize) {
+            wr32le(dst, (uint32_t)fi->contentSize); wr32le(dst + 4, (uint32_t)(fi->contentSize >> 32));
+            dst += 8;
+        }
+        *dst = (uint8_t)(Lizard_XXH32(headerStart, (size_t)(dst - headerStart), 0) >> 8);            /* :219-223 */
+        dst++;
+    }
+    return (size_t)(dst - start);
+}
+
 /* LizardF_compressBegin, lizard_frame.c:362-424 */
 size_t LizardF_compressBegin(LizardF_compressionContext_t c, void* dstBuffer, size_t dstMaxSize, const LizardF_preferences_t* prefsPtr)
 {
@@ -174,19 +193,7 @@ size_t LizardF_compressBegin(LizardF_compressionContext_t c, void* dstBuffer, si
     }
     c->tmpInSize = 0; c->totalIn = 0;
     Lizard_XXH32_reset(&c->xxh, 0);
-    wr32le(dst, LZF_MAGIC); dst += 4;                                                                /* :403-424 */
-    {
-        uint8_t* const headerStart = dst;
-        *dst++ = (uint8_t)((1u << 6) + ((c->prefs.frameInfo.blockMode & 1u) << 5) + ((c->prefs.frameInfo.contentChecksumFlag & 1u) << 2)
-                           + ((c->prefs.frameInfo.contentSize > 0) << 3));
-        *dst++ = (uint8_t)((c->prefs.frameInfo.blockSizeID & 7u) << 4);
-        if (c->prefs.frameInfo.contentSize) {
-            wr32le(dst, (uint32_t)c->prefs.frameInfo.contentSize); wr32le(dst + 4, (uint32_t)(c->prefs.frameInfo.contentSize >> 32));
-            dst += 8;
-        }
-        *dst = (uint8_t)(Lizard_XXH32(headerStart, (size_t)(dst - headerStart), 0) >> 8);            /* :219-223 */
-        dst++;
-    }
+    dst += write_header(dst, &c->prefs.frameInfo);
     c->stage = 1;
     return (size_t)(dst - (uint8_t*)dstBuffer);
 }
@@ -801,6 +808,9 @@ int LizardGPU_frameIndex(const void* srcBuffer, size_t srcSize, LizardGPU_frameI
 }
 
 size_t lzgpu_frame_block_size(unsigned blockSizeID) { return block_size_of(blockSizeID); }
+/* for lizard_frame_device.c, which answers what compress_frame(.., strict) answers */
+unsigned lzgpu_frame_optimal_bsid(unsigned requested, size_t srcSize) { return optimal_bsid(requested, srcSize); }
+size_t lzgpu_frame_write_header(uint8_t* dst, const LizardF_frameInfo_t* frameInfo) { return write_header(dst, frameInfo); }
 
 size_t LizardGPU_decompressFrameBound(const void* srcBuffer, size_t srcSize)
 {

@@ -20,6 +20,7 @@
 #include "lz_kernels.h"   // LzBatch / LzUnBatch, residency knobs, the kernels
 #include "unframe_kernels.h"   // lz_unframe_kernel: the block records of a frame (LizardGPU_decompressFrame)
 #include "unframe_walk.h"      // lz_unframe_walk_kernel: the walk over a frame in device memory (LizardGPU_decompressFrame_device)
+#include "lz_frame_pack.h"     // lz_frame_scan_kernel / lz_frame_gather_kernel: a frame assembled in device memory (LizardGPU_compressFrame_device)
 
 namespace {
 
@@ -795,6 +796,19 @@ void  lzk_pack_launch(const void* d_in, const void* d_slots, size_t slot, const 
 {
     static_assert(LZK_PACK_PAYLOAD == LZ_PACK_PAYLOAD && LZK_PACK_FRAME == LZ_PACK_FRAME, "pack modes");
     lz_pack_launch((const u8*)d_in, (const u8*)d_slots, slot, d_sizes, (u64*)d_offsets, (u8*)d_packed, nb, blockSize, lastBlockSize, mode, stream);
+}
+int   lzk_frame_pack_launch(const void* d_in, const void* d_slots, size_t slot, const uint32_t* d_sizes, uint64_t* d_offsets, void* d_dst,
+                            uint32_t nb, uint32_t blockSize, uint32_t lastBlockSize, uint64_t* d_state, uint64_t limit, hipStream_t stream)
+{
+    static_assert(sizeof(LzFrameState) == 4 * sizeof(uint64_t), "the state the host reads back");
+    if (!d_in || !d_slots || !d_sizes || !d_offsets || !d_dst || !d_state || nb == 0 || blockSize == 0 || lastBlockSize == 0 || lastBlockSize > blockSize) {
+        snprintf(t_err, sizeof t_err, "bad argument (null pointer, no blocks or lastBlockSize > blockSize)");
+        return -LIZARDGPU_ERR_ARG;
+    }
+    lz_frame_pack_launch((const u8*)d_in, (const u8*)d_slots, slot, d_sizes, (u64*)d_offsets, (u8*)d_dst, nb, blockSize, lastBlockSize,
+                         (LzFrameState*)d_state, limit, stream);
+    LZ_HIP(hipGetLastError());
+    return 0;
 }
 
 #ifdef LZ_PROFILE

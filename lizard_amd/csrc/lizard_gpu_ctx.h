@@ -85,6 +85,7 @@ typedef struct LzCtx {
      * pinned buffers are the stages' */
     uint8_t* dfTab;     size_t dfTabCap;
     unsigned long long devFrameStats[4];  /* LizardGPU_frameDecodeDeviceStats; since process start */
+    unsigned long long devFrameCompressStats[4];   /* LizardGPU_frameCompressDeviceStats (lizard_frame_device.c); since process start */
     LzStage stage[LZ_STAGES];
     LzCombine comb;
     pthread_mutex_t mu;
@@ -137,6 +138,12 @@ int   lzk_launch_unframe_inplace(LzCtx* c, const void* d_src, const uint64_t* d_
 /* exclusive scan of the record sizes + compaction of the valid bytes into d_packed (lz_pack.h); mode: LZK_PACK_* */
 void  lzk_pack_launch(const void* d_in, const void* d_slots, size_t slot, const uint32_t* d_sizes, uint64_t* d_offsets, void* d_packed,
                       uint32_t nb, uint32_t blockSize, uint32_t lastBlockSize, int mode, hipStream_t stream);
+/* one chunk of a frame assembled in device memory (lz_frame_pack.h): the frame records of nb blocks — slots as lzk_launch left them,
+ * raw input at d_in — go to d_dst + (the cursor of *d_state + their prefix sum); the cursor advances, the overflow flag of *d_state
+ * rises when it passes `limit`, and no record that ends behind `limit` is written.  d_state: 4 x uint64 in device memory
+ * (cursor, overflow, raw records, reserved) */
+int   lzk_frame_pack_launch(const void* d_in, const void* d_slots, size_t slot, const uint32_t* d_sizes, uint64_t* d_offsets, void* d_dst,
+                            uint32_t nb, uint32_t blockSize, uint32_t lastBlockSize, uint64_t* d_state, uint64_t limit, hipStream_t stream);
 /* lizard_pipeline_host.c: its staging helpers, shared with lizard_unframe_host.c */
 int    lzp_ensure_dev(LzCtx* c, void** p, size_t* cap, size_t need);
 int    lzp_ensure_pinned(void** p, size_t* cap, size_t need);
