@@ -510,10 +510,12 @@ LZ_DEV void lz_slot_pos(u32 ip, u32 special, u32 slot, u32 mflimit, u32& p, bool
 // Backward extension of a winner (fast.h:102) from the bytes its lane fetched: cb = equal bytes in the 8 before position and
 // candidate (0 when the candidate starts less than 8 bytes into the block: nothing was fetched).  Exact when the run ends inside
 // those bytes or at the limit (anchor, start of the block), else 0xFFFF = unresolved (lz_count_back finishes it).  Wave-uniform.
+// (bitwise on purpose: with || and && the wave-uniform form is three scalar branches, this one is none)
 LZ_DEV u32 lz_back_from(u32 cb, u32 P, u32 M, u32 anchor)
 {
     const u32 roomB = (P - anchor) < M ? (P - anchor) : M;
-    return (roomB <= cb || (M >= 8u && cb < 8u)) ? (cb < roomB ? cb : roomB) : 0xFFFFu;
+    const u32 exact = (u32)(roomB <= cb) | ((u32)(M >= 8u) & (u32)(cb < 8u));
+    return exact ? (cb < roomB ? cb : roomB) : 0xFFFFu;
 }
 
 // Memory-latency structure of a round (the parse is latency-bound: ~70 % of wave time is s_waitcnt):
@@ -584,171 +586,172 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
     if constexpr (kNarrow) validNext = validNext && lane < kW0;
     nextBytes = lz_ld64(src + (validNext ? pNext : S));
     u32 W = kW0;            // uniform: slots of the round about to run
+    u32 v0 = 0;             // uniform: slots consumed by earlier rounds of this run
+    // ONE loop: an iteration is a round of W slots; a round with a winner goes on to extend and push its match and to set up the
+    // next run, a round without one moves on inside its run.  (As a loop of rounds inside a loop of runs the two exits of the inner
+    // loop, "winner" and "ran into mflimit", were lowered to a state code and a ladder of ~30 scalar instructions and 8 uniform
+    // branches behind every round: profiles/producer_round_isa_before.txt.)
     for (;;) {
-        // ---------------- search: rounds of 64 slots until a lane accepts ----------------
-        u32 v0 = 0;         // uniform: slots consumed by earlier rounds of this run
-        u32 P = 0, M = 0, ml = 0, back = 0;   // uniform: winner position, candidate, lengths
-        for (;;) {
-            LZ_PROF(st, 3);                                              // loop glue, sequence push
-            const u32 p = pNext; const bool valid = validNext, putOnly = putOnlyNext;
-            const u64 bytes = nextBytes;
-            u32 pAhead;                                                  // my slot's position in the next round of this run
-            {
-                lz_slot_pos(ip, special, v0 + W + lane, mflimit, pAhead, validNext, putOnlyNext);
-                if constexpr (kNarrow) validNext = validNext && lane < (W < 32u ? 2u * W : 64u);
-                pNext = pAhead;
-                if (!validNext) pAhead = S;                              // any readable address
-            }
-            if constexpr (TAB::kSweeps) {   // keep every live slot younger than 2^17 positions (see LzTab)
-                const u32 p0 = lz_readlane(p, 0);
-                if (p0 >= st.sweepAt) { lz_tab_sweep<HASHLOG>(table, p0, false); st.sweepAt = p0 + TAB::kSweepEvery; table.sync(); }
-            }
-            // (slots past mflimit hold stale bytes and a meaningless hash; `valid` keeps them out of every decision
-            //  and their stores go to the trash slot — the round itself is branch-free up to the candidate batch)
-            const u32 first4 = (u32)bytes;
-            const u32 h = lz_hash5<HASHLOG>(bytes);
-            const u32 mine = table.entry(p, first4);
-            u32 e;                                                       // fast.h:86: the slot as this visit finds it
-            u64 grp = laneBit;                                           // lanes of this round on my table slot (not needed with kXchg)
-            u32 eOld = 0;
-            u32 jPrev = 64u;                                             // kTagDedup: the lane my `e` came from (64 = the table)
-            if constexpr (TAB::kXchg) {
-                // fast.h:86-88 for all 64 visits in one LDS trip: every lane exchanges its entry into its slot; lanes that share a
-                // slot are served in lane order, so each gets back what the reference's serial walk would have found there.
-                // Visits after the winner never happened: they are taken back once the winner is known (below).
-                e = table.xchg(valid ? h : (1u << HASHLOG), mine);
-            } else {
-            e = table.get(h, p);                                         // value before this round
-            bool lost;
-            if constexpr (TAB::kTagDedup) {                              // same-slot lanes found through LDS; nothing stored yet
-                const u32 ti = h & table.tagMask;
-                if (valid) table.tag[ti] = (u8)lane;
-                lz_lds_sync();
-                lost = valid && table.tag[ti] != (u8)lane;
-                lz_lds_sync();                                           // reads done before the next round's writes
-            } else {
-                lz_converge();                                           // every lane has read before any lane puts
-                table.set(valid ? h : (1u << HASHLOG), mine);            // speculative put (fast.h:88); undone below if needed
-                table.sync();
-                // two slots of this round on one table slot: the later must see the earlier's put, in order
-                lost = valid && table.lostPut(h, mine);
-            }
-            u64 pend = lz_ballot(lost);                                  // uniform
-            eOld = e;
-            if (pend) {
-                while (pend) {
-                    const u32 f = lz_ctz64(pend);
-                    const u32 hv = lz_readlane(h, f);
-                    const bool same = valid && h == hv;
-                    const u64 g = lz_ballot(same);
-                    if (same) grp = g;
-                    pend &= ~g;
-                }
-                const u64 prev = grp & lanesBelow;
-                const u32 j = prev ? 63u - lz_clz64(prev) : lane;
-                const u32 ej = lz_shfl(mine, j);
-                if (prev) { e = ej; jPrev = j; }
-            }
-            }
-            // accept test, fast.h:90-97 (check bits first: they decide whether any bytes are fetched)
-            const u32 age = table.age(p, e);
-            const u32 ep = p - age;
-            const bool cand = valid && !putOnly && table.sameCheck(e, mine) && age >= LZ_MIN_OFFSET && age <= LZ_MAX_DIST_LZ4
-                           && age <= p - lowPos;
-            u64 cA = LZ_ANY64, cB = LZ_ANY64, pB = LZ_ANY64, cC = LZ_ANY64, pC = LZ_ANY64, cZ = LZ_ANY64, pZ = LZ_ANY64;   // (read by `cand` lanes only)
-            const bool haveBack = cand && ep >= 8u;                      // then p >= 16 as well
-            const bool have24 = p + 24u <= E;                            // third 8 bytes readable inside the sub-block
-            if (cand) {                                                  // one batch, straight-line (p + 16 <= E - 5)
-                const u32 zb = haveBack ? 8u : 0u, fc = have24 ? 16u : 0u;
-                cA = lz_ld64(src + ep); cB = lz_ld64(src + ep + 8u); pB = lz_ld64(src + p + 8u);
-                cC = lz_ld64(src + (ep + fc)); pC = lz_ld64(src + (p + fc));     // (32-bit offsets from one scalar base: no 64-bit address math)
-                cZ = lz_ld64(src + (ep - zb)); pZ = lz_ld64(src + (p - zb));
-            }
-            // source bytes for the next round of this run (consumed only if no lane accepts).  Always
-            // issued and assigned unconditionally: no select forces the load to complete inside this
-            // round and the vmcnt arithmetic of the batch above stays exact.
-            nextBytes = lz_ld64(src + pAhead);
-            LZ_PROF(st, 0);                                              // round part A: bytes wait, hash, LDS, filter, loads issued
-            // match lengths from the batch, already clamped like the reference's counts (fast.h:100,102):
-            // exact when the difference (or the limit) lies inside the fetched bytes, else 0xFFFF = unresolved
-            bool ok = false;
-            u32 fwd = 0xFFFFu, cbk = 0u;
-#ifdef LZ_SKIP_NOCAND
-            if (lz_ballot(cand))                                         // most rounds have no candidate at all: no batch, nothing to measure
-#endif
-            {
-                ok = cand && (u32)cA == first4;                          // fast.h:97
-                const u64 x = bytes ^ cA, y = pB ^ cB, y2 = pC ^ cC, z = pZ ^ cZ;
-                const u32 seen = have24 ? 24u : 16u;
-                const u32 common = x ? lz_ctz64(x) >> 3 : y ? 8u + (lz_ctz64(y) >> 3) : (have24 && y2) ? 16u + (lz_ctz64(y2) >> 3) : seen;
-                const u32 room = matchlimit - p;                         // p < matchlimit for every valid slot
-                if (common < seen || room <= seen) fwd = common < room ? common : room;
-                cbk = !haveBack ? 0u : z ? lz_clz64(z) >> 3 : 8u;        // (lz_back_from turns it into the winner's backward length)
-            }
-            lz_pin(fwd); lz_pin(cbk);                                    // computed here, under this batch's counted wait
-            const u64 okMask = lz_ballot(ok);                            // uniform
-            const u64 validMask = lz_ballot(valid);                      // uniform, a prefix of lanes
-            u32 w = 0;
-            u64 commit = validMask;
-            u64 deadMask = 0;                                            // lanes inside the matches of chained sequences
-            if (okMask) {
-                w = lz_ctz64(okMask); commit = validMask & (~0ull >> (63u - w));
-                if constexpr (kChain) {
-                    while (v0 == 0) {                                    // first round of a run: consecutive positions behind the winner
-                        const u32 Pw = lz_readlane(p, w), fw = lz_readlane(fwd, w);
-                        if (fw == 0xFFFFu) break;
-                        const u32 Mw = lz_readlane(ep, w);
-                        const u32 bk = lz_back_from(lz_readlane(cbk, w), Pw, Mw, anchor);
-                        if (bk == 0xFFFFu) break;
-                        const u32 ipn = Pw + fw, l1 = w + fw;            // fast.h:141: ip behind the sequence, and its lane
-                        if (ipn > mflimit || l1 > 63u) break;
-                        const u64 from1 = ~0ull << l1;
-                        const u64 ok2 = okMask & from1;
-                        if (!ok2) break;
-                        const u32 w2 = lz_ctz64(ok2);                    // the next accepting lane: probe of ip or a visit of the next run
-                        const u64 put2 = 1ull << (l1 - 2u);              // put(ip-2), fast.h:146
-                        const u64 dead2 = deadMask | ((from1 ^ (~0ull << (w + 1u))) & ~put2);
-                        const u64 readers = put2 | (from1 & (~0ull >> (63u - w2)));
-                        // my slot's entry was written by the lane `age` below me (consecutive positions): a put that never happened?
-                        // (global tables: nothing was stored yet, the entry came from that lane's registers)
-                        const bool stale = TAB::kXchg ? (age <= lane && ((dead2 >> (lane - age)) & 1ull)) : (jPrev < 64u && ((dead2 >> jPrev) & 1ull));
-                        if (lz_ballot(stale) & readers) break;
-                        lz_seq_push<LEAN>(st, Pw - bk - anchor, fw + bk, Pw - Mw);      // fast.h:138
-                        anchor = ipn;
-                        deadMask = dead2; commit |= readers; w = w2;
-                    }
-                }
-            }
-            // settle the table slots: slots after the winner never happened (the reference stopped there)
-            if constexpr (TAB::kXchg) {
-                // Of the undone lanes on one slot, the lowest one holds in `e` what the slot must go back to (the entry of the last
-                // lane that did happen, or the value from before the round); it is the one whose `e` was not written by an undone
-                // lane: entries of this round are told from older ones by their age (positions of a round ascend).
-                const u32 pw = okMask ? lz_readlane(p, w) : 0u;
-                const bool eUndone = (p > pw && age < p - pw) || (kChain && age <= lane && ((deadMask >> (lane - age)) & 1ull));
-                const bool restore = okMask != 0 && valid && !(commit & laneBit) && !eUndone;
-                table.set(restore ? h : (1u << HASHLOG), e);
-            } else if constexpr (TAB::kTagDedup) {                       // last committed slot of every group stores, once
-                const u64 c = grp & commit;
-                table.set((valid && (c >> lane) == 1ull) ? h : (1u << HASHLOG), mine);
-            } else {
-                const u64 c = grp & commit;                              // committed slots on my table slot
-                const bool single = grp == laneBit;
-                const bool undo = single ? !(commit & laneBit)           // my own put did not happen
-                                         : (c == 0 && (grp & lanesBelow) == 0);   // whole group undone: its first lane restores
-                const bool redo = !single && c != 0 && (c >> lane) == 1ull;       // last committed slot of the group wins
-                table.set((valid && (undo || redo)) ? h : (1u << HASHLOG), undo ? eOld : mine);
-            }
+        LZ_PROF(st, 3);                                              // loop glue, sequence push
+        const u32 p = pNext; const bool valid = validNext, putOnly = putOnlyNext;
+        const u64 bytes = nextBytes;
+        u32 pAhead;                                                  // my slot's position in the next round of this run
+        {
+            lz_slot_pos(ip, special, v0 + W + lane, mflimit, pAhead, validNext, putOnlyNext);
+            if constexpr (kNarrow) validNext = validNext && lane < (W < 32u ? 2u * W : 64u);
+            pNext = pAhead;
+            if (!validNext) pAhead = S;                              // any readable address
+        }
+        if constexpr (TAB::kSweeps) {   // keep every live slot younger than 2^17 positions (see LzTab)
+            const u32 p0 = lz_readlane(p, 0);
+            if (p0 >= st.sweepAt) { lz_tab_sweep<HASHLOG>(table, p0, false); st.sweepAt = p0 + TAB::kSweepEvery; table.sync(); }
+        }
+        // (slots past mflimit hold stale bytes and a meaningless hash; `valid` keeps them out of every decision
+        //  and their stores go to the trash slot — the round itself is branch-free up to the candidate batch)
+        const u32 first4 = (u32)bytes;
+        const u32 h = lz_hash5<HASHLOG>(bytes);
+        const u32 mine = table.entry(p, first4);
+        u32 e;                                                       // fast.h:86: the slot as this visit finds it
+        u64 grp = laneBit;                                           // lanes of this round on my table slot (not needed with kXchg)
+        u32 eOld = 0;
+        u32 jPrev = 64u;                                             // kTagDedup: the lane my `e` came from (64 = the table)
+        if constexpr (TAB::kXchg) {
+            // fast.h:86-88 for all 64 visits in one LDS trip: every lane exchanges its entry into its slot; lanes that share a
+            // slot are served in lane order, so each gets back what the reference's serial walk would have found there.
+            // Visits after the winner never happened: they are taken back once the winner is known (below).
+            e = table.xchg(valid ? h : (1u << HASHLOG), mine);
+        } else {
+        e = table.get(h, p);                                         // value before this round
+        bool lost;
+        if constexpr (TAB::kTagDedup) {                              // same-slot lanes found through LDS; nothing stored yet
+            const u32 ti = h & table.tagMask;
+            if (valid) table.tag[ti] = (u8)lane;
+            lz_lds_sync();
+            lost = valid && table.tag[ti] != (u8)lane;
+            lz_lds_sync();                                           // reads done before the next round's writes
+        } else {
+            lz_converge();                                           // every lane has read before any lane puts
+            table.set(valid ? h : (1u << HASHLOG), mine);            // speculative put (fast.h:88); undone below if needed
             table.sync();
-            LZ_PROF(st, 1);                                              // round part B: candidate wait, ballots, slot settle
-            if (okMask) {
-                P = lz_readlane(p, w); M = lz_readlane(ep, w);
-                ml = lz_readlane(fwd, w); back = lz_back_from(lz_readlane(cbk, w), P, M, anchor);
-                break;
+            // two slots of this round on one table slot: the later must see the earlier's put, in order
+            lost = valid && table.lostPut(h, mine);
+        }
+        u64 pend = lz_ballot(lost);                                  // uniform
+        eOld = e;
+        if (pend) {
+            while (pend) {
+                const u32 f = lz_ctz64(pend);
+                const u32 hv = lz_readlane(h, f);
+                const bool same = valid && h == hv;
+                const u64 g = lz_ballot(same);
+                if (same) grp = g;
+                pend &= ~g;
             }
-            if (validMask != (kNarrow ? ~0ull >> (64u - W) : ~0ull)) goto tail;      // ran into mflimit without a match
+            const u64 prev = grp & lanesBelow;
+            const u32 j = prev ? 63u - lz_clz64(prev) : lane;
+            const u32 ej = lz_shfl(mine, j);
+            if (prev) { e = ej; jPrev = j; }
+        }
+        }
+        // accept test, fast.h:90-97 (check bits first: they decide whether any bytes are fetched)
+        const u32 age = table.age(p, e);
+        const u32 ep = p - age;
+        const bool cand = valid && !putOnly && table.sameCheck(e, mine) && age >= LZ_MIN_OFFSET && age <= LZ_MAX_DIST_LZ4
+                       && age <= p - lowPos;
+        u64 cA = LZ_ANY64, cB = LZ_ANY64, pB = LZ_ANY64, cC = LZ_ANY64, pC = LZ_ANY64, cZ = LZ_ANY64, pZ = LZ_ANY64;   // (read by `cand` lanes only)
+        const bool haveBack = cand && ep >= 8u;                      // then p >= 16 as well
+        const bool have24 = p + 24u <= E;                            // third 8 bytes readable inside the sub-block
+        if (cand) {                                                  // one batch, straight-line (p + 16 <= E - 5)
+            const u32 zb = haveBack ? 8u : 0u, fc = have24 ? 16u : 0u;
+            cA = lz_ld64(src + ep); cB = lz_ld64(src + ep + 8u); pB = lz_ld64(src + p + 8u);
+            cC = lz_ld64(src + (ep + fc)); pC = lz_ld64(src + (p + fc));     // (32-bit offsets from one scalar base: no 64-bit address math)
+            cZ = lz_ld64(src + (ep - zb)); pZ = lz_ld64(src + (p - zb));
+        }
+        // source bytes for the next round of this run (consumed only if no lane accepts).  Always
+        // issued and assigned unconditionally: no select forces the load to complete inside this
+        // round and the vmcnt arithmetic of the batch above stays exact.
+        nextBytes = lz_ld64(src + pAhead);
+        LZ_PROF(st, 0);                                              // round part A: bytes wait, hash, LDS, filter, loads issued
+        // match lengths from the batch, already clamped like the reference's counts (fast.h:100,102):
+        // exact when the difference (or the limit) lies inside the fetched bytes, else 0xFFFF = unresolved
+        bool ok = false;
+        u32 fwd = 0xFFFFu, cbk = 0u;
+#ifdef LZ_SKIP_NOCAND
+        if (lz_ballot(cand))                                         // most rounds have no candidate at all: no batch, nothing to measure
+#endif
+        {
+            ok = cand && (u32)cA == first4;                          // fast.h:97
+            const u64 x = bytes ^ cA, y = pB ^ cB, y2 = pC ^ cC, z = pZ ^ cZ;
+            const u32 seen = have24 ? 24u : 16u;
+            const u32 common = x ? lz_ctz64(x) >> 3 : y ? 8u + (lz_ctz64(y) >> 3) : (have24 && y2) ? 16u + (lz_ctz64(y2) >> 3) : seen;
+            const u32 room = matchlimit - p;                         // p < matchlimit for every valid slot
+            if (common < seen || room <= seen) fwd = common < room ? common : room;
+            cbk = !haveBack ? 0u : z ? lz_clz64(z) >> 3 : 8u;        // (lz_back_from turns it into the winner's backward length)
+        }
+        lz_pin(fwd); lz_pin(cbk);                                    // computed here, under this batch's counted wait
+        const u64 okMask = lz_ballot(ok);                              // uniform
+        const u64 validMask = lz_ballot(valid);                        // uniform, a prefix of lanes
+        u32 w = 0;
+        u64 commit = validMask;
+        u64 deadMask = 0;                                            // lanes inside the matches of chained sequences
+        u32 P = 0, M = 0, ml = 0, back = 0;                          // uniform: winner position, candidate, lengths
+        if (okMask) {
+            w = lz_ctz64(okMask); commit = validMask & (~0ull >> (63u - w));
+            // The winner's record is read ONCE per winner: a winner that chains is pushed from it, the last one leaves the loop with
+            // it (P, M, ml, back).  The four reads do not depend on each other; lz_back_from is branch-free.
+            for (;;) {
+                P = lz_readlane(p, w); M = lz_readlane(ep, w); ml = lz_readlane(fwd, w);
+                back = lz_back_from(lz_readlane(cbk, w), P, M, anchor);
+                if constexpr (!kChain) break;
+                // first round of a run: consecutive positions behind the winner
+                if (v0 != 0 || (ml | back) == 0xFFFFu) break;        // (lengths from the batch are < 32: the OR is 0xFFFF iff one is unresolved)
+                const u32 ipn = P + ml, l1 = w + ml;                 // fast.h:141: ip behind the sequence, and its lane
+                if (ipn > mflimit || l1 > 63u) break;
+                const u64 from1 = ~0ull << l1;
+                const u64 ok2 = okMask & from1;
+                if (!ok2) break;
+                const u32 w2 = lz_ctz64(ok2);                        // the next accepting lane: probe of ip or a visit of the next run
+                const u64 put2 = 1ull << (l1 - 2u);                  // put(ip-2), fast.h:146
+                const u64 dead2 = deadMask | ((from1 ^ (~0ull << (w + 1u))) & ~put2);
+                const u64 readers = put2 | (from1 & (~0ull >> (63u - w2)));
+                // my slot's entry was written by the lane `age` below me (consecutive positions): a put that never happened?
+                // (global tables: nothing was stored yet, the entry came from that lane's registers)
+                const bool stale = TAB::kXchg ? (age <= lane && ((dead2 >> (lane - age)) & 1ull)) : (jPrev < 64u && ((dead2 >> jPrev) & 1ull));
+                if (lz_ballot(stale) & readers) break;
+                lz_seq_push<LEAN>(st, P - back - anchor, ml + back, P - M);      // fast.h:138
+                anchor = ipn;
+                deadMask = dead2; commit |= readers; w = w2;
+            }
+        }
+        // settle the table slots: slots after the winner never happened (the reference stopped there)
+        if constexpr (TAB::kXchg) {
+            // Without a winner every exchange of the round stands: nothing to settle.
+            // Of the undone lanes on one slot, the lowest one holds in `e` what the slot must go back to (the entry of the last
+            // lane that did happen, or the value from before the round); it is the one whose `e` was not written by an undone
+            // lane: entries of this round are told from older ones by their age (positions of a round ascend).
+            if (okMask) {
+                const bool eUndone = (p > P && age < p - P) || (kChain && age <= lane && ((deadMask >> (lane - age)) & 1ull));
+                const bool restore = valid && !(commit & laneBit) && !eUndone;
+                table.set(restore ? h : (1u << HASHLOG), e);
+            }
+        } else if constexpr (TAB::kTagDedup) {                       // last committed slot of every group stores, once
+            const u64 c = grp & commit;
+            table.set((valid && (c >> lane) == 1ull) ? h : (1u << HASHLOG), mine);
+        } else {
+            const u64 c = grp & commit;                              // committed slots on my table slot
+            const bool single = grp == laneBit;
+            const bool undo = single ? !(commit & laneBit)           // my own put did not happen
+                                     : (c == 0 && (grp & lanesBelow) == 0);   // whole group undone: its first lane restores
+            const bool redo = !single && c != 0 && (c >> lane) == 1ull;       // last committed slot of the group wins
+            table.set((valid && (undo || redo)) ? h : (1u << HASHLOG), undo ? eOld : mine);
+        }
+        table.sync();
+        LZ_PROF(st, 1);                                              // round part B: candidate wait, ballots, slot settle
+        if (!okMask) {
+            if (validMask != (kNarrow ? ~0ull >> (64u - W) : ~0ull)) break;      // ran into mflimit without a match
             v0 += W;
             if constexpr (kNarrow) W = W < 32u ? 2u * W : 64u;
+            continue;
         }
         // ---------------- extend ----------------
         if (ml == 0xFFFFu) ml = 4u + lz_count_fwd(src, P + 4u, M + 4u, matchlimit);            // fast.h:100
@@ -778,9 +781,9 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
         nextBytes = lz_ld64(src + (validNext ? pNext : S));
         lz_seq_push<LEAN>(st, P - anchor, ml, P - M);                    // fast.h:138 (encoded later, in parallel)
         anchor = ip;
-        if (ip > mflimit) goto tail;                                     // fast.h:143
+        if (ip > mflimit) break;                                         // fast.h:143
+        v0 = 0;
     }
-tail:
     if (st.nseq & (LZ_SEQ_RING - 1u)) lz_seq_flush(st);
     st.lastLits = E - anchor; st.nlit += E - anchor;                     // fast.h:187-190
     LZ_PROF(st, 3);
