@@ -506,6 +506,36 @@ LZ_DEV void lz_slot_pos(u32 ip, u32 special, u32 slot, u32 mflimit, u32& p, bool
     valid = post || pv + lz_visit_step(v) <= mflimit;                    // fast.h:84, tested before the probe
     putOnly = post && slot == 0;
 }
+// The schedule without its general form (lz_parse_fast, rounds of 64 slots).  For visits 0..64 the offset is the visit itself and the
+// step is 1 (q = 0 in lz_visit_off), so the FIRST round of a run is a row of consecutive positions behind its post-match slots:
+LZ_DEV void lz_slot_pos_first(u32 ip, u32 special, u32 lane, u32 mflimit, u32& p, bool& valid, bool& putOnly)
+{
+    putOnly = special && lane == 0;                                      // put(ip-2); lane 1 = the probe of ip; lanes >= 2 = visits 0.. from ip+1
+    p = ip + lane - special - (putOnly ? 1u : 0u);
+    valid = (special && lane < 2u) || p + 1u <= mflimit;
+}
+// and for the LATER rounds no special case can occur (visit >= 62): from lz_visit_off, (32q + t)(q + 1) -> (32(q + 1) + t)(q + 2),
+// f(v + 64) = f(v) + v + 63, and the step of visit v is (v + 63) >> 6.  A lane carries the position of its slot in the coming round
+// (pA) and s = v + 63 (sA): the round after it is pA + sA, sA + 64.  Seeded where a run is set up.
+LZ_DEV void lz_slot_seed(u32 ip, u32 special, u32 lane, u32& pA, u32& sA)
+{
+    const u32 v = 64u + lane - 2u * special;                             // my visit in the second round of the run
+    pA = ip + special + lz_visit_off(v);                                 // (special is a constant at every call: a per-lane constant + ip)
+    sA = v + 63u;
+}
+// Lane mask (wave-uniform, an SGPR pair) -> "is my bit set", as the condition of a select without a shift and a compare per lane.
+LZ_DEV bool lz_lane_in(u64 mask)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__has_builtin)
+#if __has_builtin(__builtin_amdgcn_inverse_ballot_w64)
+    return __builtin_amdgcn_inverse_ballot_w64(mask);
+#else
+    return (mask >> lz_lane()) & 1ull;
+#endif
+#else
+    return (mask >> lz_lane()) & 1ull;
+#endif
+}
 
 // Backward extension of a winner (fast.h:102) from the bytes its lane fetched: cb = equal bytes in the 8 before position and
 // candidate (0 when the candidate starts less than 8 bytes into the block: nothing was fetched).  Exact when the run ends inside
@@ -556,12 +586,19 @@ LZ_DEV u32 lz_back_from(u32 cb, u32 P, u32 M, u32 anchor)
 // (Measured in round 5 and not kept, profiles/r05j_m_*: 32 bytes forward in the candidate batch instead of 24 — two more loads per
 //  candidate lane — is 5.3 % SLOWER at level 10 (191.9 vs 202.7 GB/s) although it halves the matches that need a second trip; 16
 //  bytes forward is the same as 24 within 0.3 %.)
-template <int HASHLOG, class TAB, bool LEAN = false>
+// LZ_STAT(8..12) below count paths for the test emulator (tests/emul); on the device LZ_STAT is empty and what only feeds a mark
+// (`nch`, the second test behind a stale stop, the fourth-round test) is dead code — marked "emulator only" where it stands.
+// LANEFORMS (the level-10 producers): the chain loop's dead set kept per reader and the slot schedule as a recurrence, both below.
+// Every other instantiation keeps the mask form and lz_slot_pos: the level-30 kernel sits at its 128-VGPR limit and either form
+// costs it scalar spills (profiles/producer_chain_ab.txt), levels 11 / 31 take their entry from lane jPrev and run narrow rounds.
+template <int HASHLOG, class TAB, bool LEAN = false, bool LANEFORMS = false>
 LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStreams& st)
 {
     constexpr bool kChain = (TAB::kXchg || TAB::kTagDedup) && LZ_FAST_CHAIN;   // several sequences out of one round (see below)
     constexpr bool kNarrow = TAB::kTagDedup && LZ_WIDE_W0 < 64u;
     constexpr u32  kW0 = kNarrow ? LZ_WIDE_W0 : 64u;
+    constexpr bool kRecur = LANEFORMS && !kNarrow;                        // rounds of 64 slots: the schedule as a recurrence (lz_slot_seed)
+    constexpr bool kLaneChain = LANEFORMS && kChain && TAB::kXchg;   // the chain's dead set kept per reader (below)
     const u32 lane = lz_lane();
     const u64 laneBit = 1ull << lane;
     const u64 lanesBelow = laneBit - 1ull;
@@ -582,9 +619,12 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
     // next run): the visit-schedule arithmetic and the source load are off the round's critical path
     u32 pNext; bool validNext, putOnlyNext;
     u64 nextBytes;
-    lz_slot_pos(ip, 0u, lane, mflimit, pNext, validNext, putOnlyNext);
+    if constexpr (kRecur) lz_slot_pos_first(ip, 0u, lane, mflimit, pNext, validNext, putOnlyNext);
+    else lz_slot_pos(ip, 0u, lane, mflimit, pNext, validNext, putOnlyNext);
     if constexpr (kNarrow) validNext = validNext && lane < kW0;
     nextBytes = lz_ld64(src + (validNext ? pNext : S));
+    u32 pA = 0, sA = 0;                                              // kRecur: my slot of the round after the coming one
+    if constexpr (kRecur) lz_slot_seed(ip, 0u, lane, pA, sA);
     u32 W = kW0;            // uniform: slots of the round about to run
     u32 v0 = 0;             // uniform: slots consumed by earlier rounds of this run
     // ONE loop: an iteration is a round of W slots; a round with a winner goes on to extend and push its match and to set up the
@@ -596,7 +636,12 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
         const u32 p = pNext; const bool valid = validNext, putOnly = putOnlyNext;
         const u64 bytes = nextBytes;
         u32 pAhead;                                                  // my slot's position in the next round of this run
-        {
+        if constexpr (kRecur) {
+            pAhead = pA; validNext = pA + (sA >> 6) <= mflimit; putOnlyNext = false;    // fast.h:84
+            pA += sA; sA += 64u;
+            pNext = pAhead;
+            if (!validNext) pAhead = S;                              // any readable address
+        } else {
             lz_slot_pos(ip, special, v0 + W + lane, mflimit, pAhead, validNext, putOnlyNext);
             if constexpr (kNarrow) validNext = validNext && lane < (W < 32u ? 2u * W : 64u);
             pNext = pAhead;
@@ -656,6 +701,9 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
         // accept test, fast.h:90-97 (check bits first: they decide whether any bytes are fetched)
         const u32 age = table.age(p, e);
         const u32 ep = p - age;
+        // kLaneChain: the lane that wrote my slot's entry, when it is one of this round (first round of a run: consecutive positions,
+        // so it sits `age` lanes below me); an older entry gives a number far above 63.  Fixed for the round, computed here.
+        const u32 wr = lane - age;
         const bool cand = valid && !putOnly && table.sameCheck(e, mine) && age >= LZ_MIN_OFFSET && age <= LZ_MAX_DIST_LZ4
                        && age <= p - lowPos;
         u64 cA = LZ_ANY64, cB = LZ_ANY64, pB = LZ_ANY64, cC = LZ_ANY64, pC = LZ_ANY64, cZ = LZ_ANY64, pZ = LZ_ANY64;   // (read by `cand` lanes only)
@@ -694,6 +742,8 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
         u32 w = 0;
         u64 commit = validMask;
         u64 deadMask = 0;                                            // lanes inside the matches of chained sequences
+        u64 wdead = 0;                                               // kLaneChain instead: lanes whose entry was written by such a lane
+        u32 nch = 0;                                                 // emulator only: sequences pushed by the chain (mark 8)
         u32 P = 0, M = 0, ml = 0, back = 0;                          // uniform: winner position, candidate, lengths
         if (okMask) {
             w = lz_ctz64(okMask); commit = validMask & (~0ull >> (63u - w));
@@ -706,21 +756,36 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
                 // first round of a run: consecutive positions behind the winner
                 if (v0 != 0 || (ml | back) == 0xFFFFu) break;        // (lengths from the batch are < 32: the OR is 0xFFFF iff one is unresolved)
                 const u32 ipn = P + ml, l1 = w + ml;                 // fast.h:141: ip behind the sequence, and its lane
-                if (ipn > mflimit || l1 > 63u) break;
+                if (ipn > mflimit) break;
+                if (l1 > 63u) { LZ_STAT(11); break; }
                 const u64 from1 = ~0ull << l1;
                 const u64 ok2 = okMask & from1;
                 if (!ok2) break;
                 const u32 w2 = lz_ctz64(ok2);                        // the next accepting lane: probe of ip or a visit of the next run
-                const u64 put2 = 1ull << (l1 - 2u);                  // put(ip-2), fast.h:146
-                const u64 dead2 = deadMask | ((from1 ^ (~0ull << (w + 1u))) & ~put2);
-                const u64 readers = put2 | (from1 & (~0ull >> (63u - w2)));
-                // my slot's entry was written by the lane `age` below me (consecutive positions): a put that never happened?
-                // (global tables: nothing was stored yet, the entry came from that lane's registers)
-                const bool stale = TAB::kXchg ? (age <= lane && ((dead2 >> (lane - age)) & 1ull)) : (jPrev < 64u && ((dead2 >> jPrev) & 1ull));
-                if (lz_ballot(stale) & readers) break;
+                // The lanes inside this match, (w, l1) without l1 - 2 = put(ip-2) (fast.h:146), made puts that never happened.  The
+                // sequence may be pushed if no reader up to the next winner, {l1 - 2} and [l1, w2], found one of them in its slot —
+                // or one of an earlier pass of this loop: the dead set accumulates.
+                u64 readers;
+                if constexpr (kLaneChain) {
+                    // per reader: "my writer is dead", two range compares against the scalars; every mask is a v_cmp's result
+                    const u64 wdead2 = wdead | (lz_ballot(wr - (w + 1u) < ml - 1u) & lz_ballot(wr != l1 - 2u));
+                    readers = lz_ballot(lane - l1 <= w2 - l1) | lz_ballot(lane == l1 - 2u);
+                    if (wdead2 & readers) { LZ_STAT(9); if (wdead & readers) LZ_STAT(10); break; }      // (inner test: emulator only)
+                    wdead = wdead2;
+                } else {
+                    const u64 put2 = 1ull << (l1 - 2u);
+                    const u64 dead2 = deadMask | ((from1 ^ (~0ull << (w + 1u))) & ~put2);
+                    readers = put2 | (from1 & (~0ull >> (63u - w2)));
+                    // my slot's entry was written by the lane `age` below me (consecutive positions): a put that never happened?
+                    // (global tables: nothing was stored yet, the entry came from that lane's registers)
+                    const auto stale = [&](u64 dead) { return TAB::kXchg ? (age <= lane && ((dead >> (lane - age)) & 1ull)) : (jPrev < 64u && ((dead >> jPrev) & 1ull)); };
+                    if (lz_ballot(stale(dead2)) & readers) { LZ_STAT(9); if (lz_ballot(stale(deadMask)) & readers) LZ_STAT(10); break; }   // (inner test: emulator only)
+                    deadMask = dead2;
+                }
                 lz_seq_push<LEAN>(st, P - back - anchor, ml + back, P - M);      // fast.h:138
                 anchor = ipn;
-                deadMask = dead2; commit |= readers; w = w2;
+                commit |= readers; w = w2;
+                if (++nch == 3u) LZ_STAT(8);                                 // emulator only
             }
         }
         // settle the table slots: slots after the winner never happened (the reference stopped there)
@@ -730,9 +795,14 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
             // lane that did happen, or the value from before the round); it is the one whose `e` was not written by an undone
             // lane: entries of this round are told from older ones by their age (positions of a round ascend).
             if (okMask) {
-                const bool eUndone = (p > P && age < p - P) || (kChain && age <= lane && ((deadMask >> (lane - age)) & 1ull));
-                const bool restore = valid && !(commit & laneBit) && !eUndone;
-                table.set(restore ? h : (1u << HASHLOG), e);
+                if constexpr (kLaneChain) {
+                    const u64 undone = (lz_ballot(p > P) & lz_ballot(age < p - P)) | wdead;
+                    table.set(lz_lane_in(validMask & ~commit & ~undone) ? h : (1u << HASHLOG), e);
+                } else {
+                    const bool eUndone = (p > P && age < p - P) || (kChain && age <= lane && ((deadMask >> (lane - age)) & 1ull));
+                    const bool restore = valid && !(commit & laneBit) && !eUndone;
+                    table.set(restore ? h : (1u << HASHLOG), e);
+                }
             }
         } else if constexpr (TAB::kTagDedup) {                       // last committed slot of every group stores, once
             const u64 c = grp & commit;
@@ -750,6 +820,7 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
         if (!okMask) {
             if (validMask != (kNarrow ? ~0ull >> (64u - W) : ~0ull)) break;      // ran into mflimit without a match
             v0 += W;
+            if (v0 >= 160u && v0 - W < 160u) LZ_STAT(12);                        // emulator only: the run's fourth round comes
             if constexpr (kNarrow) W = W < 32u ? 2u * W : 64u;
             continue;
         }
@@ -775,7 +846,8 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
         // as soon as the winner's forward length is known, is slower: 159.3 vs 171.6 GB/s, profiles/r03g_* — a conditional load of
         // a loop-carried value makes every round's wait a vmcnt(0).)
         special = 1u;
-        lz_slot_pos(ip, 1u, lane, mflimit, pNext, validNext, putOnlyNext);
+        if constexpr (kRecur) { lz_slot_pos_first(ip, 1u, lane, mflimit, pNext, validNext, putOnlyNext); lz_slot_seed(ip, 1u, lane, pA, sA); }
+        else lz_slot_pos(ip, 1u, lane, mflimit, pNext, validNext, putOnlyNext);
         if constexpr (kNarrow) { W = kW0; validNext = validNext && lane < kW0; }
         if (ip > mflimit) validNext = false;                             // (fast.h:143: there is no next run; any readable address)
         nextBytes = lz_ld64(src + (validNext ? pNext : S));

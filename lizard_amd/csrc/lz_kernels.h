@@ -181,7 +181,7 @@ __global__ __launch_bounds__(64 * (HUF ? LZ_SPLIT_PROD_HUF + LZ_SPLIT_CONS_HUF :
     s.dst = a.dst; s.dstStride = a.dstStride; s.sizes = a.sizes; s.level = a.level; s.counter = a.counter;
     s.arena = a.scratch + (u64)blockIdx.x * LZ_MAX_WAVES * LZ_SCRATCH_BYTES; s.nProd = NP; s.nCons = NC; s.nBufs = NB; s.qn = QN;
     s.srcSizes = a.srcSizes; s.srcOffsets = a.srcOffsets; s.activeProd = a.activeWaves < NP ? a.activeWaves : NP;
-    if (wave < NP) lz_split_producer<12>(s, sh, wave, (void*)tables[wave < NP ? wave : 0], rings[wave < NP ? wave : 0]);
+    if (wave < NP) lz_split_producer<12, !HUF>(s, sh, wave, (void*)tables[wave < NP ? wave : 0], rings[wave < NP ? wave : 0]);
     else           lz_split_consumer<HUF>(s, sh, wave - NP, hufWs[HUF ? wave - NP : 0]);
 }
 

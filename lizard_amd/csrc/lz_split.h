@@ -75,7 +75,7 @@ LZ_DEV u8* lz_split_staging(const LzSplitArgs& a, u32 cons) { return a.arena + (
 #define LZ_SPLIT_PROF_END ((u64)16u * LZ_SCRATCH_BYTES)       // profile builds: 16 x 128-byte records at the end of the workgroup's arena (LZ_MAX_WAVES slots)
 
 // ---- producer: claim blocks, parse their sub-blocks, publish one job per sub-block ----
-template <int HASHLOG>
+template <int HASHLOG, bool LANEFORMS = true>                    // (lz_parse_fast: true for the level-10 kernel)
 LZ_DEV void lz_split_producer(const LzSplitArgs& a, const LzSplitShared& sh, u32 prod, void* tableMem, u64* seqRing)
 {
     const u32 lane = lz_lane();
@@ -116,7 +116,7 @@ LZ_DEV void lz_split_producer(const LzSplitArgs& a, const LzSplitShared& sh, u32
 #if LZ_FAST_128
             lz_parse_fast128<HASHLOG>(src, pos, pos + part, tab, st);
 #else
-            lz_parse_fast<HASHLOG, LzTab, LZ_SPLIT_LEAN != 0>(src, pos, pos + part, tab, st);
+            lz_parse_fast<HASHLOG, LzTab, LZ_SPLIT_LEAN != 0, LANEFORMS>(src, pos, pos + part, tab, st);
 #endif
             // the job header
             {
