@@ -438,6 +438,32 @@ size_t LizardGPU_compressFrame_device(void* d_dst, size_t dstCapacity, const voi
  * launched, [3] source bytes copied to the host for the checksum.  0 or -LIZARDGPU_ERR_*. */
 int    LizardGPU_frameCompressDeviceStats(unsigned long long out[4]);
 
+/* ---- many buffers in device memory, one frame each, in ONE batch ----
+ * d_dsts, dstCapacities, d_srcs, srcSizes and results are HOST arrays of nFrames entries; the pointers they hold are device pointers
+ * on the selected device.  Per frame i, results[i] and the bytes d_dsts[i][0 .. results[i]) are what
+ * LizardGPU_compressFrame_device(d_dsts[i], dstCapacities[i], d_srcs[i], srcSizes[i], preferencesPtr, stream) answers — and so, by
+ * that function's contract, what LizardGPU_compressFrame answers: its refusals in its order, GENERIC for a null pointer in a frame's
+ * entry, the level clamp, the block size id shrunk to EACH frame's own input (frames of one batch may have different block sizes and
+ * header bytes), contentSize != 0 meaning "write this frame's srcSize", srcSize == 0, dstMaxSize_tooSmall for the 1-byte last block at
+ * exactly the bound.  A refused frame does not stop the others; one refused up front (everything but that last case) leaves its d_dst
+ * untouched.  Nothing outside d_dsts[i][0 .. dstCapacities[i]) is written, nothing outside d_srcs[i][0 .. srcSizes[i]) is read;
+ * sources may start at any byte address.  Destinations that overlap each other or a source are the caller's error.
+ * Returns 0 once every results[i] has been decided this way (LizardGPU_lastError names the first refused frame, if any);
+ * -LIZARDGPU_ERR_ARG for a null array with nFrames > 0; -LIZARDGPU_ERR_* when the machinery fails (no device, HIP, allocation:
+ * LizardGPU_lastError has the text), and then every frame not already refused gets LIZARDGPU_FRAME_ERR_GENERIC.  nFrames == 0
+ * returns 0 and touches nothing.  Never a host fall-back, never blocks stored raw instead.
+ * SYNCHRONOUS like its single-frame sibling: ordered after what `stream` holds at the call; on return all frames are visible to work
+ * enqueued on `stream` afterwards.
+ * The blocks of all frames form one list that is compressed in chunks (LIZARDGPU_CHUNK_MB over the batch's largest block size;
+ * LIZARDGPU_FRAME_CHUNK_BLOCKS as above), so a batch of small buffers fills the device as one large buffer does, and the host waits
+ * once per call.  NO payload byte crosses PCIe in either direction, checksum or not: what crosses is a table entry per frame and per
+ * block going up and a result record per frame coming down.  The content checksums are computed on the device, all frames side by
+ * side; ONE frame's XXH32 is serial, so a batch cannot finish before its largest frame is hashed, at a per-frame rate that is not
+ * measured yet and certainly below a host core's — one huge buffer with a checksum belongs with LizardGPU_compressFrame_device.
+ * LizardGPU_frameCompressDeviceStats counts this entry's blocks and chunks in [0], [1], [2]; it never adds to [3]. */
+int    LizardGPU_compressFrames_device(size_t nFrames, void* const* d_dsts, const size_t* dstCapacities, const void* const* d_srcs,
+                                       const size_t* srcSizes, size_t* results, const LizardGPU_framePrefs_t* preferencesPtr, void* stream);
+
 /* Streaming form.  LizardGPU_cctx_t replaces LizardF_compressionContext_t (lib/lizard_frame.h:145); the functions
  * replace LizardF_createCompressionContext / _freeCompressionContext (:157-158, int result: 0 or -LIZARDGPU_FRAME_ERR_*),
  * LizardF_compressBegin (:169), LizardF_compressBound (:178), LizardF_compressUpdate (:190), LizardF_flush (:202) and

@@ -98,6 +98,8 @@ def lib():
     L.LizardGPU_compressFrame_device.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
     L.LizardGPU_compressFrame_device.restype = c.c_size_t
     L.LizardGPU_frameCompressDeviceStats.argtypes = [c.c_void_p]; L.LizardGPU_frameCompressDeviceStats.restype = c.c_int
+    L.LizardGPU_compressFrames_device.argtypes = [c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+    L.LizardGPU_compressFrames_device.restype = c.c_int
     _lib = L
     return L
 

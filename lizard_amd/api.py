@@ -184,6 +184,46 @@ def compress_frame_device(src, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksu
     return dst, n
 
 
+def compress_frames_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksum=False, content_size=False):
+    """One Lizard frame for each of `tensors`, a sequence of contiguous uint8 CUDA tensors on one device (zero-length ones allowed),
+    in ONE call of LizardGPU_compressFrames_device on torch's current stream: frame i is the bytes compress_frame_device writes for
+    tensor i.  No payload crosses PCIe, with or without `checksum`.  One output tensor holds every frame's
+    LizardGPU_compressFrameBound-sized region at 256-byte-aligned offsets; returns the list of views region_i[:n_i].  A refused frame
+    raises LizardAmdError naming the first such frame's index and error; so does a failure of the machinery."""
+    import torch
+    L = _lib.lib()
+    tensors = list(tensors)
+    if not tensors:
+        return []
+    device = tensors[0].device
+    for t in tensors:
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.device == device
+    n = len(tensors)
+    p = _FramePrefs()
+    p.frameInfo.blockSizeID = block_size_id
+    p.frameInfo.blockMode = 1
+    p.frameInfo.contentChecksumFlag = 1 if checksum else 0
+    p.frameInfo.contentSize = 1 if content_size else 0          # (non-zero: "write each frame's own size")
+    p.compressionLevel = level
+    sizes = (ctypes.c_size_t * n)(*[int(t.numel()) for t in tensors])
+    caps = (ctypes.c_size_t * n)(*[_lib.check_frame(L.LizardGPU_compressFrameBound(s, ctypes.byref(p)), "LizardGPU_compressFrameBound") for s in sizes])
+    offsets, total = [], 0
+    for cap in caps:
+        offsets.append(total)
+        total += (cap + 255) & ~255
+    out = torch.empty(total, dtype=torch.uint8, device=device)
+    srcs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors])
+    dsts = (ctypes.c_void_p * n)(*[out.data_ptr() + o for o in offsets])
+    results = (ctypes.c_size_t * n)()
+    L.LizardGPU_setDevice(device.index or 0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    _lib.check(L.LizardGPU_compressFrames_device(n, dsts, caps, srcs, sizes, results, ctypes.byref(p), stream), "LizardGPU_compressFrames_device")
+    for i, r in enumerate(results):
+        if L.LizardGPU_frameIsError(r):
+            raise _lib.LizardAmdError(f"LizardGPU_compressFrames_device: frame {i}: {L.LizardF_getErrorName(r).decode()}")
+    return [out[o:o + int(r)] for o, r in zip(offsets, results)]
+
+
 def frame_info(data):
     """Header fields and record table of the frame at the start of `data` (host code, no GPU): a dict with block_size_id,
     independent, checksum, skippable, content_size, n_records, frame_bytes, bound."""

@@ -2,8 +2,8 @@
  * device memory (include/lizard_amd.h Part 3).  Plain C on the HIP runtime's C API and the shim of lizard_gpu_ctx.h, like
  * lizard_unframe_device.c, whose producing counterpart it is.  It answers what LizardGPU_compressFrame (lizard_frame_host.c,
  * compress_frame with strict = 1) answers for the same bytes, preferences and capacity: the refusals are made here in that function's
- * order with its own helpers (lzgpu_frame_optimal_bsid, lzgpu_frame_block_size, lzgpu_frame_write_header), the records are what
- * lzgpu_frame_records packs.
+ * order by lzgpu_frame_device_plan of that file (which LizardGPU_compressFrames_device, lizard_frames_device.c, calls per frame too), the
+ * header is lzgpu_frame_write_header's, the records are what lzgpu_frame_records packs.
  *
  * No payload byte crosses PCIe.  The input is cut into chunks of whole blocks (lzp_chunk_bytes; LIZARDGPU_FRAME_CHUNK_BLOCKS
  * overrides the blocks per chunk).  A chunk is compressed by the block kernels into the bound-sized slots of one of the three stages
@@ -45,8 +45,9 @@
 #define LZC_E(code)       ((size_t)-(long)(LIZARDGPU_FRAME_ERR_##code))
 
 size_t   lzgpu_frame_block_size(unsigned blockSizeID);       /* lizard_frame_host.c */
-unsigned lzgpu_frame_optimal_bsid(unsigned requested, size_t srcSize);
 size_t   lzgpu_frame_write_header(uint8_t* dst, const LizardF_frameInfo_t* frameInfo);
+size_t   lzgpu_frame_device_plan(LizardF_preferences_t* prefs, const LizardF_preferences_t* prefsPtr, const void* d_dst, size_t dstCapacity,
+                                 const void* d_src, size_t srcSize);
 
 /* the small pinned area of a call (stage 0's h_aux): header, the state the cursor starts from, the state read back, end mark + checksum */
 enum { LZC_H_HEADER = 0, LZC_H_INIT = 32, LZC_H_RESULT = 64, LZC_H_TAIL = 96, LZC_H_BYTES = 128 };
@@ -204,26 +205,16 @@ size_t LizardGPU_compressFrame_device(void* d_dst, size_t dstCapacity, const voi
     LizardF_preferences_t prefs;
     CJob j;
     LzGuard g;
-    size_t result = 0, frameEnd, bound;
+    size_t result, frameEnd;
     int rc;
     lzk_err()[0] = 0;
     /* compress_frame, LizardF_compressBegin and LizardF_compressUpdate of lizard_frame_host.c, in their order */
-    if (preferencesPtr) prefs = *preferencesPtr; else memset(&prefs, 0, sizeof prefs);
-    if (prefs.frameInfo.contentSize != 0) prefs.frameInfo.contentSize = (unsigned long long)srcSize;
-    prefs.frameInfo.blockSizeID = (LizardF_blockSizeID_t)lzgpu_frame_optimal_bsid((unsigned)prefs.frameInfo.blockSizeID, srcSize);
-    prefs.autoFlush = 1;
-    if (!lzgpu_frame_block_size((unsigned)prefs.frameInfo.blockSizeID)) return c_refuse(LZC_E(maxBlockSize_invalid));
-    if (srcSize <= lzgpu_frame_block_size((unsigned)prefs.frameInfo.blockSizeID)) prefs.frameInfo.blockMode = (LizardF_blockMode_t)1;
-    bound = LizardGPU_compressFrameBound(srcSize, &prefs);
-    if (dstCapacity < bound) return c_refuse(LZC_E(dstMaxSize_tooSmall));
-    if (!d_dst || (!d_src && srcSize)) { snprintf(lzk_err(), LZK_ERR_BYTES, "bad argument (null pointer)"); return LZC_E(GENERIC); }
-    if (prefs.frameInfo.blockSizeID == 0) prefs.frameInfo.blockSizeID = (LizardF_blockSizeID_t)1;
+    result = lzgpu_frame_device_plan(&prefs, preferencesPtr, d_dst, dstCapacity, d_src, srcSize);
+    if (result == LZC_E(GENERIC)) { snprintf(lzk_err(), LZK_ERR_BYTES, "bad argument (null pointer)"); return result; }
+    if (result) return c_refuse(result);
     memset(&j, 0, sizeof j);
     j.blockSize = lzgpu_frame_block_size((unsigned)prefs.frameInfo.blockSizeID);
     j.level = lzk_clamp_level(prefs.compressionLevel);
-    if (prefs.frameInfo.frameType != 0) return c_refuse(LZC_E(frameType_unknown));
-    if (prefs.frameInfo.blockMode != 1) return c_refuse(LZC_E(blockMode_invalid));
-    if (!LizardGPU_levelSupported(j.level)) return c_refuse(LZC_E(compressionLevel_invalid));
     frameEnd = 4 + (size_t)prefs.frameInfo.contentChecksumFlag * 4;
 
     j.src = (const uint8_t*)d_src; j.srcSize = srcSize; j.dst = (uint8_t*)d_dst; j.cap = dstCapacity;

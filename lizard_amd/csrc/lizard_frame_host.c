@@ -811,6 +811,27 @@ size_t lzgpu_frame_block_size(unsigned blockSizeID) { return block_size_of(block
 /* for lizard_frame_device.c, which answers what compress_frame(.., strict) answers */
 unsigned lzgpu_frame_optimal_bsid(unsigned requested, size_t srcSize) { return optimal_bsid(requested, srcSize); }
 size_t lzgpu_frame_write_header(uint8_t* dst, const LizardF_frameInfo_t* frameInfo) { return write_header(dst, frameInfo); }
+/* What compress_frame(.., strict), LizardF_compressBegin and LizardF_compressUpdate decide before the first block, in their order, for
+ * the entries whose buffers lie in device memory (lizard_frame_device.c, lizard_frames_device.c): 0 and *prefs as the frame is to be
+ * written (content size, the block size id shrunk to the input and never 0, the block mode), or the code they refuse with.  GENERIC:
+ * a null pointer. */
+size_t lzgpu_frame_device_plan(LizardF_preferences_t* prefs, const LizardF_preferences_t* prefsPtr, const void* d_dst, size_t dstCapacity,
+                               const void* d_src, size_t srcSize)
+{
+    if (prefsPtr) *prefs = *prefsPtr; else memset(prefs, 0, sizeof *prefs);
+    if (prefs->frameInfo.contentSize != 0) prefs->frameInfo.contentSize = (unsigned long long)srcSize;
+    prefs->frameInfo.blockSizeID = (LizardF_blockSizeID_t)optimal_bsid((unsigned)prefs->frameInfo.blockSizeID, srcSize);
+    prefs->autoFlush = 1;
+    if (!block_size_of((unsigned)prefs->frameInfo.blockSizeID)) return LZF_ERR(maxBlockSize_invalid);
+    if (srcSize <= block_size_of((unsigned)prefs->frameInfo.blockSizeID)) prefs->frameInfo.blockMode = (LizardF_blockMode_t)1;
+    if (dstCapacity < LizardF_compressFrameBound(srcSize, prefs)) return LZF_ERR(dstMaxSize_tooSmall);
+    if (!d_dst || (!d_src && srcSize)) return LZF_ERR(GENERIC);
+    if (prefs->frameInfo.blockSizeID == 0) prefs->frameInfo.blockSizeID = (LizardF_blockSizeID_t)1;
+    if (prefs->frameInfo.frameType != 0) return LZF_ERR(frameType_unknown);
+    if (prefs->frameInfo.blockMode != 1) return LZF_ERR(blockMode_invalid);
+    if (!LizardGPU_levelSupported(clamp_level(prefs->compressionLevel))) return LZF_ERR(compressionLevel_invalid);
+    return 0;
+}
 
 size_t LizardGPU_decompressFrameBound(const void* srcBuffer, size_t srcSize)
 {

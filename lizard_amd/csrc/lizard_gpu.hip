@@ -21,6 +21,7 @@
 #include "unframe_kernels.h"   // lz_unframe_kernel: the block records of a frame (LizardGPU_decompressFrame)
 #include "unframe_walk.h"      // lz_unframe_walk_kernel: the walk over a frame in device memory (LizardGPU_decompressFrame_device)
 #include "lz_frame_pack.h"     // lz_frame_scan_kernel / lz_frame_gather_kernel: a frame assembled in device memory (LizardGPU_compressFrame_device)
+#include "lz_frames_pack.h"    // the same for a batch of frames, and their checksums (LizardGPU_compressFrames_device)
 
 namespace {
 
@@ -807,6 +808,33 @@ int   lzk_frame_pack_launch(const void* d_in, const void* d_slots, size_t slot, 
     }
     lz_frame_pack_launch((const u8*)d_in, (const u8*)d_slots, slot, d_sizes, (u64*)d_offsets, (u8*)d_dst, nb, blockSize, lastBlockSize,
                          (LzFrameState*)d_state, limit, stream);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
+int   lzk_frames_pack_launch(const void* d_base, const uint64_t* d_blkOffsets, const uint32_t* d_blkSizes, const uint32_t* d_blkFrames,
+                             const void* d_slots, size_t slot, const uint32_t* d_sizes, uint64_t* d_offsets, uint32_t nb,
+                             LzFramesEntry* d_frames, hipStream_t stream)
+{
+    if (!d_base || !d_blkOffsets || !d_blkSizes || !d_blkFrames || !d_slots || !d_sizes || !d_offsets || !d_frames || nb == 0) {
+        snprintf(t_err, sizeof t_err, "bad argument (null pointer or no blocks)");
+        return -LIZARDGPU_ERR_ARG;
+    }
+    lz_frames_pack_launch((const u8*)d_base, (const u64*)d_blkOffsets, d_blkSizes, d_blkFrames, (const u8*)d_slots, slot, d_sizes, (u64*)d_offsets,
+                          nb, d_frames, stream);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
+int   lzk_frames_hash_launch(LzFramesEntry* d_frames, uint32_t nFrames, hipStream_t stream)
+{
+    if (!d_frames || nFrames == 0) { snprintf(t_err, sizeof t_err, "bad argument (null pointer or no frames)"); return -LIZARDGPU_ERR_ARG; }
+    lz_frames_hash_launch(d_frames, nFrames, stream);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
+int   lzk_frames_finish_launch(const LzFramesEntry* d_frames, LzFramesResult* d_results, uint32_t nFrames, hipStream_t stream)
+{
+    if (!d_frames || !d_results || nFrames == 0) { snprintf(t_err, sizeof t_err, "bad argument (null pointer or no frames)"); return -LIZARDGPU_ERR_ARG; }
+    lz_frames_finish_launch(d_frames, d_results, nFrames, stream);
     LZ_HIP(hipGetLastError());
     return 0;
 }

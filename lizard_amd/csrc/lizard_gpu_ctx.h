@@ -82,7 +82,7 @@ typedef struct LzCtx {
     unsigned long long unframeStats[5];   /* LizardGPU_frameDecodeStats [0..3], [4] = chunks packed on the device; since process start */
     /* LizardGPU_decompressFrame_device / LizardGPU_frameIndex_device (lizard_unframe_device.c): the record tables, per-record results
      * and result records of the two walk segments in flight (device, counted in devBytes) and its statistics; its staging slots and
-     * pinned buffers are the stages' */
+     * pinned buffers are the stages'.  LizardGPU_compressFrames_device (lizard_frames_device.c) keeps the tables of a call here too. */
     uint8_t* dfTab;     size_t dfTabCap;
     unsigned long long devFrameStats[4];  /* LizardGPU_frameDecodeDeviceStats; since process start */
     unsigned long long devFrameCompressStats[4];   /* LizardGPU_frameCompressDeviceStats (lizard_frame_device.c); since process start */
@@ -144,6 +144,32 @@ void  lzk_pack_launch(const void* d_in, const void* d_slots, size_t slot, const 
  * (cursor, overflow, raw records, reserved) */
 int   lzk_frame_pack_launch(const void* d_in, const void* d_slots, size_t slot, const uint32_t* d_sizes, uint64_t* d_offsets, void* d_dst,
                             uint32_t nb, uint32_t blockSize, uint32_t lastBlockSize, uint64_t* d_state, uint64_t limit, hipStream_t stream);
+/* LizardGPU_compressFrames_device (lizard_frames_device.c, lz_frames_pack.h): one entry per frame of the batch, in device memory for
+ * the whole call.  The host fills everything; the device advances cursor, raises overflow, counts rawRecords and sets hash. */
+typedef struct LzFramesEntry {
+    uint64_t dst, limit;                /* the frame's place (a device address); capacity minus end mark and checksum */
+    uint64_t cursor;                    /* where the next record goes: starts at headerBytes */
+    uint64_t src, srcSize;              /* what the checksum covers (a device address) */
+    uint32_t overflow, rawRecords;      /* sticky: the cursor passed the limit; blocks stored raw so far */
+    uint32_t blockSize, nBlocks;        /* (the host's own notes: the kernels find a frame's blocks through the per-block frame index) */
+    uint32_t hash, headerBytes, flags;  /* LZK_FRAMES_* */
+    uint8_t  header[20];                /* lzgpu_frame_write_header's bytes (at most 15) */
+} LzFramesEntry;
+typedef struct LzFramesResult { uint64_t size; uint32_t rawRecords, reserved; } LzFramesResult;   /* size: the frame's, or LZK_FRAMES_OVERFLOW */
+#define LZK_FRAMES_LIVE      1u         /* not refused by the host: the kernels leave every other entry and its d_dst alone */
+#define LZK_FRAMES_CHECKSUM  2u
+#define LZK_FRAMES_OVERFLOW  (~(uint64_t)0)
+/* one chunk of the batch (lz_frames_pack.h): block b of the chunk is d_blkSizes[b] bytes at d_base + d_blkOffsets[b] and belongs to
+ * frame d_blkFrames[b] (blocks of one frame are neighbours); its record — slot b as lzk_launch left it, or that input — goes to
+ * the frame's dst + (the frame's cursor + the record bytes of the frame's earlier blocks in this chunk), written to d_offsets[b];
+ * cursors advance, and no record that ends behind its frame's limit is written */
+int   lzk_frames_pack_launch(const void* d_base, const uint64_t* d_blkOffsets, const uint32_t* d_blkSizes, const uint32_t* d_blkFrames,
+                             const void* d_slots, size_t slot, const uint32_t* d_sizes, uint64_t* d_offsets, uint32_t nb,
+                             LzFramesEntry* d_frames, hipStream_t stream);
+/* XXH32 (seed 0) of every live entry's source that asks for a checksum -> its hash */
+int   lzk_frames_hash_launch(LzFramesEntry* d_frames, uint32_t nFrames, hipStream_t stream);
+/* header, end mark and checksum of every live entry, and every entry's result record */
+int   lzk_frames_finish_launch(const LzFramesEntry* d_frames, LzFramesResult* d_results, uint32_t nFrames, hipStream_t stream);
 /* lizard_pipeline_host.c: its staging helpers, shared with lizard_unframe_host.c */
 int    lzp_ensure_dev(LzCtx* c, void** p, size_t* cap, size_t need);
 int    lzp_ensure_pinned(void** p, size_t* cap, size_t need);
