@@ -13,7 +13,8 @@
  *   Part 1d  XXH32 / XXH64          lib/xxhash/xxhash.h         (XXH_NAMESPACE=Lizard_, lib/Makefile:52)
  *   Part 2   batch extension (ours): many independent blocks per call, host- or device-resident, several GPUs, decompression
  *   Part 3   the strict frame twins of rounds 2-3 (LizardGPU_compressFrame ...)
- *   Part 3b  whole-frame decompression on the GPU (LizardGPU_decompressFrame, LizardGPU_decompressFrame_device ...)
+ *   Part 3b  whole-frame decompression on the GPU (LizardGPU_decompressFrame, LizardGPU_decompressFrame_device,
+ *            LizardGPU_decompressFrames_device ...)
  *
  * Plain C, plain pointers and sizes; no HIP or torch types in any signature (a HIP stream is passed
  * as an opaque void*).
@@ -562,6 +563,44 @@ int LizardGPU_frameDecodeDeviceStats(unsigned long long out[4]);
  * size of a frame's block size id (0 = the default id; 0 for an id above 7). */
 size_t LizardGPU_frameWalkRecords(void);
 size_t LizardGPU_frameBlockSize(unsigned blockSizeID);
+
+/* ---- MANY frames in device memory, each decoded into its own device buffer, in ONE batch ----
+ * The reading half of LizardGPU_compressFrames_device: a state_dict, cache pages, a list of activations.  Frame i lies at d_srcs[i]
+ * (srcSizes[i] bytes) and decodes into d_dsts[i] (dstCapacities[i] bytes); d_dsts, dstCapacities, d_srcs, srcSizes, results and
+ * srcConsumed (may be NULL) are HOST arrays of nFrames entries.  results[i], srcConsumed[i] and the bytes d_dsts[i][0 .. results[i])
+ * are what LizardGPU_decompressFrame_device(d_dsts[i], dstCapacities[i], d_srcs[i], srcSizes[i], &used, flags, stream) answers — and
+ * so, by that function's contract, what LizardGPU_decompressFrame answers for the same bytes: intact and damaged frames, every
+ * capacity, LIZARDGPU_FRAME_SKIP_CHECKSUM honoured, a skippable frame decodes to 0 bytes.  A null pointer in an entry with a non-zero
+ * size is LIZARDGPU_FRAME_ERR_GENERIC for that frame only; a refused frame does not stop the others.  Nothing outside
+ * d_dsts[i][0 .. dstCapacities[i]) is written, nothing outside d_srcs[i][0 .. srcSizes[i]) is read; sources and destinations may start
+ * at any byte address.  Overlapping destinations are the caller's error; several entries may share a source.
+ * The host waits TWICE per call, however many frames: every frame is walked on the device side by side (one wave each) to count its
+ * records; then the walk that fills the record tables, ONE decode launch over all records of all frames (each in place in its frame's
+ * buffer), the per-frame settling, the content checksums — XXH32 of the decoded bytes ON THE DEVICE, sixteen frames per wave — and the
+ * comparison with the stored ones are enqueued together.  No payload byte crosses PCIe, checksum or not.
+ * The device settles the frames LizardGPU_compressFrames_device writes (every record but the last fills the frame's block size).  A
+ * frame the walk accepts that is anything else — a short record in the middle (flushed frames), a block that fails or needs its
+ * history (the reference's linked frames), a buffer that is too small, a wrong content size or checksum — is handed to
+ * LizardGPU_decompressFrame_device after the batch part, one call each; [2] of the statistics counts them.
+ * Returns 0 once every results[i] has been decided (LizardGPU_lastError names the first refused frame); -LIZARDGPU_ERR_ARG for a null
+ * array with nFrames > 0, or when nFrames or the batch's record count is 2^32 or more; -LIZARDGPU_ERR_* when the machinery fails:
+ * every frame not yet decided then answers LIZARDGPU_FRAME_ERR_GENERIC with 0 bytes consumed.  nFrames == 0 returns 0 and touches
+ * nothing.  SYNCHRONOUS and ordered after what `stream` holds, like LizardGPU_decompressFrame_device.  Never a host fall-back for a
+ * frame of this library. */
+int LizardGPU_decompressFrames_device(size_t nFrames, void* const* d_dsts, const size_t* dstCapacities, const void* const* d_srcs,
+                                      const size_t* srcSizes, size_t* results, size_t* srcConsumed, unsigned flags, void* stream);
+
+/* LizardGPU_frameIndex_device without tables for nFrames frames, in one launch and one host wait: codes[i] is what that function
+ * returns for frame i, infos[i] is filled exactly where it fills *info, nRecords[i] / frameBytes[i] are its values (0 for a refused
+ * frame).  Any of the four output arrays (host arrays) may be NULL.  0, or -LIZARDGPU_ERR_* (null input array, 2^32 frames or more,
+ * a failure of the machinery: every codes[i] is -LIZARDGPU_FRAME_ERR_GENERIC then). */
+int LizardGPU_framesInfo_device(size_t nFrames, const void* const* d_srcs, const size_t* srcSizes, LizardGPU_frameInfo_t* infos,
+                                size_t* nRecords, size_t* frameBytes, int* codes, void* stream);
+
+/* LizardGPU_decompressFrames_device since process start, selected device: [0] records decoded by the batch kernel, [1] frames
+ * settled on the device, [2] frames handed to LizardGPU_decompressFrame_device, [3] batch calls that launched anything.
+ * 0 or -LIZARDGPU_ERR_*. */
+int LizardGPU_framesDecodeDeviceStats(unsigned long long out[4]);
 
 #ifdef __cplusplus
 }

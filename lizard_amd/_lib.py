@@ -100,6 +100,12 @@ def lib():
     L.LizardGPU_frameCompressDeviceStats.argtypes = [c.c_void_p]; L.LizardGPU_frameCompressDeviceStats.restype = c.c_int
     L.LizardGPU_compressFrames_device.argtypes = [c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
     L.LizardGPU_compressFrames_device.restype = c.c_int
+    L.LizardGPU_decompressFrames_device.argtypes = [c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint,
+                                                    c.c_void_p]
+    L.LizardGPU_decompressFrames_device.restype = c.c_int
+    L.LizardGPU_framesInfo_device.argtypes = [c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+    L.LizardGPU_framesInfo_device.restype = c.c_int
+    L.LizardGPU_framesDecodeDeviceStats.argtypes = [c.c_void_p]; L.LizardGPU_framesDecodeDeviceStats.restype = c.c_int
     _lib = L
     return L
 

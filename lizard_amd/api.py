@@ -325,3 +325,81 @@ def decompress_frame_device(src, dst=None, verify_checksum=True):
         out += n
         pos += used.value
     return dst[:out]
+
+
+def _frame_ptrs(frames):
+    import torch
+    device = frames[0].device
+    for t in frames:
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.device == device
+    n = len(frames)
+    return device, (ctypes.c_void_p * n)(*[t.data_ptr() for t in frames]), (ctypes.c_size_t * n)(*[int(t.numel()) for t in frames])
+
+
+def frames_info_device(frames):
+    """LizardGPU_framesInfo_device: the header fields and record counts of `frames`, a sequence of contiguous uint8 CUDA tensors on one
+    device that hold one frame each, all walked on the device side by side in one launch on torch's current stream, with one host
+    wait.  A list of dicts with the keys of frame_info except "bound" (and without the tables of frame_index_device).  A refused
+    frame raises LizardAmdError naming the first such frame's index and error."""
+    import torch
+    L = _lib.lib()
+    frames = list(frames)
+    if not frames:
+        return []
+    device, srcs, sizes = _frame_ptrs(frames)
+    n = len(frames)
+    infos, nrec, fbytes, codes = (_FrameInfo * n)(), (ctypes.c_size_t * n)(), (ctypes.c_size_t * n)(), (ctypes.c_int * n)()
+    L.LizardGPU_setDevice(device.index or 0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    _lib.check(L.LizardGPU_framesInfo_device(n, srcs, sizes, infos, nrec, fbytes, codes, stream), "LizardGPU_framesInfo_device")
+    for i, rc in enumerate(codes):
+        if rc:
+            raise _lib.LizardAmdError(f"LizardGPU_framesInfo_device: frame {i}: {L.LizardF_getErrorName((1 << 64) + rc).decode()}")
+    return [{"block_size_id": f.blockSizeID, "independent": bool(f.blockMode), "checksum": bool(f.contentChecksumFlag),
+             "skippable": bool(f.frameType), "content_size": f.contentSize, "n_records": int(k), "frame_bytes": int(b)}
+            for f, k, b in zip(infos, nrec, fbytes)]
+
+
+def decompress_frames_device(frames, sizes=None, verify_checksum=True):
+    """Decode `frames`, a sequence of contiguous uint8 CUDA tensors on one device that hold ONE frame each (what compress_frames_device
+    returns), in ONE call of LizardGPU_decompressFrames_device on torch's current stream: neither the frames nor the decoded bytes
+    cross PCIe, with or without verify_checksum — the content checksums are computed on the device.  One output tensor holds every
+    frame's region at 256-byte-aligned offsets; returns the list of views region_i[:n_i].
+    With `sizes`, the caller's known decoded sizes, region i has exactly sizes[i] bytes and no extra walk is made.  Without, one
+    frames_info_device call sizes region i: the header's content size when it has one, else n_records times
+    LizardGPU_frameBlockSize(block_size_id).  Both are upper bounds of the decoded size; the second is looser than
+    LizardGPU_decompressFrameBound (it counts a stored-raw record as a whole block too), by less than one block per stored-raw record.
+    Exact sizes cost nothing but one case: a frame whose last block is ONE byte is decoded by the single-frame entry when its region
+    has no room to spare (that block's record is longer than the byte it decodes to); the answer is the same.
+    A refused frame raises LizardAmdError naming the first such frame's index and error; so does a tensor with bytes behind its frame,
+    and a failure of the machinery."""
+    import torch
+    L = _lib.lib()
+    frames = list(frames)
+    if not frames:
+        return []
+    device, srcs, src_sizes = _frame_ptrs(frames)
+    n = len(frames)
+    if sizes is None:
+        infos = frames_info_device(frames)
+        sizes = [0 if f["skippable"] else f["content_size"] or f["n_records"] * L.LizardGPU_frameBlockSize(f["block_size_id"]) for f in infos]
+    sizes = [int(s) for s in sizes]
+    assert len(sizes) == n
+    offsets, total = [], 0
+    for cap in sizes:
+        offsets.append(total)
+        total += (cap + 255) & ~255
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=device)
+    dsts = (ctypes.c_void_p * n)(*[out.data_ptr() + o for o in offsets])
+    results, used = (ctypes.c_size_t * n)(), (ctypes.c_size_t * n)()
+    L.LizardGPU_setDevice(device.index or 0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    flags = 0 if verify_checksum else FRAME_SKIP_CHECKSUM
+    _lib.check(L.LizardGPU_decompressFrames_device(n, dsts, (ctypes.c_size_t * n)(*sizes), srcs, src_sizes, results, used, flags, stream),
+               "LizardGPU_decompressFrames_device")
+    for i, r in enumerate(results):
+        if L.LizardGPU_frameIsError(r):
+            raise _lib.LizardAmdError(f"LizardGPU_decompressFrames_device: frame {i}: {L.LizardF_getErrorName(r).decode()}")
+        if used[i] < src_sizes[i]:
+            raise _lib.LizardAmdError(f"LizardGPU_decompressFrames_device: frame {i}: {src_sizes[i] - used[i]} bytes behind the frame's end")
+    return [out[o:o + int(r)] for o, r in zip(offsets, results)]

@@ -22,6 +22,7 @@
 #include "unframe_walk.h"      // lz_unframe_walk_kernel: the walk over a frame in device memory (LizardGPU_decompressFrame_device)
 #include "lz_frame_pack.h"     // lz_frame_scan_kernel / lz_frame_gather_kernel: a frame assembled in device memory (LizardGPU_compressFrame_device)
 #include "lz_frames_pack.h"    // the same for a batch of frames, and their checksums (LizardGPU_compressFrames_device)
+#include "unframes_kernels.h"  // a batch of frames walked, decoded and settled in device memory (LizardGPU_decompressFrames_device)
 
 namespace {
 
@@ -590,6 +591,26 @@ int launch_walk(Ctx& c, const void* d_src, size_t srcSize, size_t startPos, size
     return 0;
 }
 
+// All records of a batch of frames, each decoded in place in its own frame's buffer (unframes_kernels.h).  Arena and counter as above.
+int launch_unframes(Ctx& c, const LzUnframesEntry* d_frames, const u64* d_offs, const u32* d_words, const u32* d_recFrame, u32* d_out,
+                    size_t nRecords, hipStream_t stream)
+{
+    if (!d_frames || !d_offs || !d_words || !d_recFrame || !d_out || nRecords == 0 || nRecords > 0xFFFFFFFFu) {
+        snprintf(t_err, sizeof t_err, "bad argument (null pointer or no records)");
+        return -LIZARDGPU_ERR_ARG;
+    }
+    int rc = ctx_init(c);
+    if (rc) return rc;
+    LzArena& own = c.arena[0];
+    LzUnframesBatch a;
+    a.frames = d_frames; a.offs = d_offs; a.words = d_words; a.recFrame = d_recFrame; a.out = d_out; a.nRecords = (u32)nRecords;
+    a.scratch = own.scratch; a.counter = own.counter;
+    u32 grid = (u32)((nRecords + LZ_WAVES_DEC - 1) / LZ_WAVES_DEC);
+    if (grid > (u32)c.cus) grid = (u32)c.cus;
+    c.hostKernelMs = -1.0f;
+    return enqueue_on(c, own, stream, nullptr, nullptr, [&] { hipLaunchKernelGGL(lz_unframes_kernel, dim3(grid), dim3(64 * LZ_WAVES_DEC), 0, stream, a); });
+}
+
 }  // namespace
 
 #include "lizard_shard.h"   // single-process multi-device entry + RCCL size gather (uses Guard / launch above)
@@ -835,6 +856,37 @@ int   lzk_frames_finish_launch(const LzFramesEntry* d_frames, LzFramesResult* d_
 {
     if (!d_frames || !d_results || nFrames == 0) { snprintf(t_err, sizeof t_err, "bad argument (null pointer or no frames)"); return -LIZARDGPU_ERR_ARG; }
     lz_frames_finish_launch(d_frames, d_results, nFrames, stream);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
+int   lzk_unframes_walk_launch(const LzUnframesEntry* d_frames, uint32_t nFrames, int fill, uint64_t* d_offs, uint32_t* d_words,
+                               struct LzWalkResult* d_res, hipStream_t stream)
+{
+    if (!d_frames || !d_res || nFrames == 0 || (fill && (!d_offs || !d_words))) { snprintf(t_err, sizeof t_err, "bad argument (null pointer or no frames)"); return -LIZARDGPU_ERR_ARG; }
+    hipLaunchKernelGGL(lz_unframes_walk_kernel, dim3((nFrames + LZU_WALK_WAVES - 1u) / LZU_WALK_WAVES), dim3(64 * LZU_WALK_WAVES), 0, stream, d_frames, nFrames,
+                       fill ? LZU_DECODE : LZU_WALK, fill ? (u64*)d_offs : nullptr, fill ? d_words : nullptr, d_res);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
+int   lzk_unframes_decode_launch(LzCtx* c, const LzUnframesEntry* d_frames, const uint64_t* d_offs, const uint32_t* d_words, const uint32_t* d_recFrame,
+                                 uint32_t* d_out, size_t nRecords, hipStream_t stream)
+{
+    return launch_unframes(*c, d_frames, (const u64*)d_offs, d_words, d_recFrame, d_out, nRecords, stream);
+}
+int   lzk_unframes_settle_launch(const LzUnframesEntry* d_frames, uint32_t nFrames, const uint32_t* d_out, LzUnframesResult* d_results,
+                                 LzFramesEntry* d_hashTab, hipStream_t stream)
+{
+    if (!d_frames || !d_out || !d_results || !d_hashTab || nFrames == 0) { snprintf(t_err, sizeof t_err, "bad argument (null pointer or no frames)"); return -LIZARDGPU_ERR_ARG; }
+    hipLaunchKernelGGL(lz_unframes_settle_kernel, dim3((nFrames + LZU_WALK_WAVES - 1u) / LZU_WALK_WAVES), dim3(64 * LZU_WALK_WAVES), 0, stream, d_frames, nFrames,
+                       d_out, d_results, d_hashTab);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
+int   lzk_unframes_finish_launch(const LzUnframesEntry* d_frames, uint32_t nFrames, const LzFramesEntry* d_hashTab, LzUnframesResult* d_results,
+                                 hipStream_t stream)
+{
+    if (!d_frames || !d_hashTab || !d_results || nFrames == 0) { snprintf(t_err, sizeof t_err, "bad argument (null pointer or no frames)"); return -LIZARDGPU_ERR_ARG; }
+    hipLaunchKernelGGL(lz_unframes_finish_kernel, dim3((nFrames + 255u) / 256u), dim3(256), 0, stream, d_frames, nFrames, d_hashTab, d_results);
     LZ_HIP(hipGetLastError());
     return 0;
 }

@@ -82,10 +82,12 @@ typedef struct LzCtx {
     unsigned long long unframeStats[5];   /* LizardGPU_frameDecodeStats [0..3], [4] = chunks packed on the device; since process start */
     /* LizardGPU_decompressFrame_device / LizardGPU_frameIndex_device (lizard_unframe_device.c): the record tables, per-record results
      * and result records of the two walk segments in flight (device, counted in devBytes) and its statistics; its staging slots and
-     * pinned buffers are the stages'.  LizardGPU_compressFrames_device (lizard_frames_device.c) keeps the tables of a call here too. */
+     * pinned buffers are the stages'.  LizardGPU_compressFrames_device (lizard_frames_device.c) keeps the tables of a call here too, and so
+     * does LizardGPU_decompressFrames_device (lizard_unframes_device.c). */
     uint8_t* dfTab;     size_t dfTabCap;
     unsigned long long devFrameStats[4];  /* LizardGPU_frameDecodeDeviceStats; since process start */
     unsigned long long devFrameCompressStats[4];   /* LizardGPU_frameCompressDeviceStats (lizard_frame_device.c); since process start */
+    unsigned long long devFramesDecodeStats[4];    /* LizardGPU_framesDecodeDeviceStats (lizard_unframes_device.c); since process start */
     LzStage stage[LZ_STAGES];
     LzCombine comb;
     pthread_mutex_t mu;
@@ -170,6 +172,21 @@ int   lzk_frames_pack_launch(const void* d_base, const uint64_t* d_blkOffsets, c
 int   lzk_frames_hash_launch(LzFramesEntry* d_frames, uint32_t nFrames, hipStream_t stream);
 /* header, end mark and checksum of every live entry, and every entry's result record */
 int   lzk_frames_finish_launch(const LzFramesEntry* d_frames, LzFramesResult* d_results, uint32_t nFrames, hipStream_t stream);
+/* LizardGPU_decompressFrames_device (lizard_unframes_device.c, unframes_kernels.h): the four launches over a batch of frames in device
+ * memory.  walk: one wave per frame whose flags have LZU_WALK (fill = 0: no tables) or LZU_DECODE (fill = 1: frame f's records go to
+ * d_offs / d_words + first_f); d_res[f] tells how frame f's walk ended.  decode: record r of frame d_recFrame[r] in place in that
+ * frame's buffer, d_out[r] = size / 0xFFFFFFFE (needs history) / 0xFFFFFFFF.  settle: d_results[f] = clean with its size, or delegate;
+ * d_hashTab[f].srcSize = the bytes lz_xxh32_frames_kernel is to hash.  finish: content size and checksum of the clean frames. */
+struct LzUnframesEntry;
+struct LzUnframesResult;
+int   lzk_unframes_walk_launch(const struct LzUnframesEntry* d_frames, uint32_t nFrames, int fill, uint64_t* d_offs, uint32_t* d_words,
+                               struct LzWalkResult* d_res, hipStream_t stream);
+int   lzk_unframes_decode_launch(LzCtx* c, const struct LzUnframesEntry* d_frames, const uint64_t* d_offs, const uint32_t* d_words,
+                                 const uint32_t* d_recFrame, uint32_t* d_out, size_t nRecords, hipStream_t stream);
+int   lzk_unframes_settle_launch(const struct LzUnframesEntry* d_frames, uint32_t nFrames, const uint32_t* d_out, struct LzUnframesResult* d_results,
+                                 LzFramesEntry* d_hashTab, hipStream_t stream);
+int   lzk_unframes_finish_launch(const struct LzUnframesEntry* d_frames, uint32_t nFrames, const LzFramesEntry* d_hashTab,
+                                 struct LzUnframesResult* d_results, hipStream_t stream);
 /* lizard_pipeline_host.c: its staging helpers, shared with lizard_unframe_host.c */
 int    lzp_ensure_dev(LzCtx* c, void** p, size_t* cap, size_t need);
 int    lzp_ensure_pinned(void** p, size_t* cap, size_t need);
