@@ -36,6 +36,12 @@
 #define LZ_HPROF_F(k) ((void)0)
 #endif
 
+// LZ_STAT marks of this file (counters in the test emulator, nothing in the product; tests/huf_stream_inputs.py names them and
+// tests/test_huf_stream_emul.py asserts which ones its streams reach): 13 RLE, 14 raw exit of a stream above 1 024 bytes, 15 depth
+// limiter, 16 / 17 its positive / negative repayment loop, 18 the latter with rankLast[1] empty, 29 the merge's general step, 30 its
+// written node register rolls over, 31 FSE / 36 nibble weight header, 53 / 56 no header (the weights' error; no nibbles above 128
+// symbols), 57 / 58 lz_fse_normalize's early return / FSE_normalizeM2, 59 the packer's partial lane group, 60 exact sizes, 61 packing.
+
 #define LZ_HUF_MAXBITS     12u    // HUF_TABLELOG_MAX, huf.h:118
 #define LZ_HUF_DEFAULTLOG  11u    // HUF_TABLELOG_DEFAULT, huf.h:119
 
@@ -121,6 +127,7 @@ LZ_DEV u32 lz_huf_set_max_height(const LzV256& leaf, LzV256& bits, u32 lastNonNu
 {
     const u32 largestBits = bits.get(lastNonNull);
     if (largestBits <= maxNbBits) return largestBits;
+    LZ_STAT(15);
     const u32 noSymbol = 0xF0F0F0F0u;
     const u32 lane = lz_lane();
     const u32 baseCost = 1u << (largestBits - maxNbBits);
@@ -153,6 +160,7 @@ LZ_DEV u32 lz_huf_set_max_height(const LzV256& leaf, LzV256& bits, u32 lastNonNu
         }
     }
     while (totalCost > 0) {
+        LZ_STAT(16);
         u32 dec = lz_highbit((u32)totalCost) + 1u;
         for (; dec > 1u; dec--) {
             const u32 highPos = rankLast.get(dec), lowPos = rankLast.get(dec - 1u);
@@ -174,7 +182,9 @@ LZ_DEV u32 lz_huf_set_max_height(const LzV256& leaf, LzV256& bits, u32 lastNonNu
         }
     }
     while (totalCost < 0) {
+        LZ_STAT(17);
         if (rankLast.get(1) == noSymbol) {
+            LZ_STAT(18);
             while (bits.get((u32)n) == maxNbBits) n--;
             bits.set((u32)(n + 1), bits.get((u32)(n + 1)) - 1u);
             rankLast.set(1, (u32)(n + 1));
@@ -221,9 +231,10 @@ LZ_DEV bool lz_fse_normalize(LzV64& norm, u32 tableLog, const LzV64& count, u32 
             still -= proba;
         }
     }
-    if (-still < ((int)norm.get(largest) >> 1)) { norm.set(largest, (u32)((int)norm.get(largest) + still)); return true; }
+    if (-still < ((int)norm.get(largest) >> 1)) { LZ_STAT(57); norm.set(largest, (u32)((int)norm.get(largest) + still)); return true; }
     // FSE_normalizeM2
     {
+        LZ_STAT(58);
         u32 distributed = 0, toDistribute;
         u64 tot = total;
         u32 lowOne = (u32)((tot * 3u) >> (tableLog + 1u));
@@ -472,6 +483,7 @@ LZ_DEV u32 lz_huf_pack_segment(const u8* src, u32 a, u32 b, u8* out, const u16* 
                 #pragma unroll
                 for (u32 g = 0; g < 4u; g++) lz_huf_pack4(wc[3u - g], ctab, acc[g], len[g]);      // group g: src[hi - 4g] .. src[hi - 4g - 3]
             } else {
+                LZ_STAT(59);
                 for (u32 j = 0; j < cnt; j++) {
                     const u32 e = ctab[src[hi - j]], g = j >> 2;
                     const u64 v = (u64)(e & 0xFFFu) << len[g];
@@ -566,6 +578,7 @@ LZ_DEV u32 lz_put_stream_huf(u8* op, const u8* stream, u32 n, u32* ws, u32* huff
     bool accept = false;                                       // uniform
     u32 csize = 0;                                             // uniform
     if (largest == n) {                                        // single symbol: RLE, 1 byte (huf_compress.c:544)
+        LZ_STAT(13);
         if (lane == 0) payload[0] = stream[0];
         lz_converge();
         csize = 1; accept = true;
@@ -649,11 +662,12 @@ LZ_DEV u32 lz_put_stream_huf(u8* op, const u8* stream, u32 n, u32* ws, u32* huff
                     }
                     li += la - la0; ni += na - na0; nodeNb += safe;
                 } else {
+                    LZ_STAT(29);
                     LZ_MERGE_DECIDE();
                     lz_writelane2(Bw, sum, Tw, dl, wa);
                     li += dl; ni += 2u - dl; nodeNb++;
                 }
-                if ((nodeNb & 63u) == 0u) { Bq.putReg(cW, Bw); T.putReg(cW, Tw); cW++; Bw = BIG; Tw = 0; }
+                if ((nodeNb & 63u) == 0u) { LZ_STAT(30); Bq.putReg(cW, Bw); T.putReg(cW, Tw); cW++; Bw = BIG; Tw = 0; }
                 if (!safe || (nodeNb & 63u) == 0u) {
                     // re-seat the registers around the cursors; the heads through the general accessors
                     cA = li >> 6; Ac = cA < 4u ? A.reg(cA) : BAR;
@@ -768,16 +782,18 @@ LZ_DEV u32 lz_put_stream_huf(u8* op, const u8* stream, u32 n, u32* ws, u32* huff
             LzBitV b;
             u32* const hlds = ws + LZ_HUF_WS_COUNT;                // the histogram's words and the leaf-parent table are free by now
             const u32 h = lz_huf_compress_weights(b, wt4, maxSym, wcount, hlds);
-            if (h == 0xFFFFFFFFu) hdr = 0;
+            if (h == 0xFFFFFFFFu) { LZ_STAT(53); hdr = 0; }
             else if (h > 1u && h < maxSym / 2u) {
+                LZ_STAT(31);
                 if (lane == 0) payload[0] = (u8)h;
                 lz_converge();
                 const u32 hw = hlds[256u + lane];
                 for (u32 k = 0; k < 4u; k++) if (4u * lane + k < h) payload[1u + 4u * lane + k] = (u8)(hw >> (8u * k));
                 hdr = h + 1u;
             }
-            else if (maxSym > 128u) hdr = 0;                   // :158 ERROR(GENERIC)
+            else if (maxSym > 128u) { LZ_STAT(56); hdr = 0; }  // :158 ERROR(GENERIC)
             else {
+                LZ_STAT(36);
                 if (lane == 0) payload[0] = (u8)(128u + (maxSym - 1u));
                 lz_converge();
                 // two weights per byte: symbols 2i, 2i+1 -> my four symbols give bytes 2*lane and 2*lane+1 (weights past maxSym-1 are 0)
@@ -828,6 +844,7 @@ LZ_DEV u32 lz_put_stream_huf(u8* op, const u8* stream, u32 n, u32* ws, u32* huff
             }
             LZ_HPROF(11);                                      // accept or not
             if (pack) {
+                LZ_STAT(61);
                 u8* q = payload + hdr + 6u;
                 u32 segBytes[4];
                 for (u32 k = 0; k < 4u; k++) {
@@ -850,6 +867,7 @@ LZ_DEV u32 lz_put_stream_huf(u8* op, const u8* stream, u32 n, u32* ws, u32* huff
         *huffed = 1;
         return 6u + csize;
     }
+    LZ_STAT(14);
     if (lane == 0) { op[0] = (u8)n; op[1] = (u8)(n >> 8); op[2] = (u8)(n >> 16); }
     lz_converge();
     for (u32 i = lane * 4u; i < (n & ~3u); i += 256u) lz_st32(op + 3 + i, lz_ld32(stream + i));

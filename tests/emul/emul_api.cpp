@@ -116,6 +116,23 @@ extern "C" int emul_put_stream_huf(const void* stream, int n, void* out, int* hu
     return (int)a.result;
 }
 
+// `count` streams one after the other through ONE workspace that is filled with 0x77 before the first and never touched between
+// them — the product runs the flag stream and the literal stream of a sub-block through the same workspace (lz_write_subblock_seq).
+// Stream i: ns[i] bytes at src + srcAt[i] -> out + outAt[i]; sizes[i] / huffed[i] receive what the stage returned.
+extern "C" void emul_put_streams_huf(const void* src, const unsigned long long* srcAt, const int* ns, int count, void* out,
+                                     const unsigned long long* outAt, int* sizes, int* huffed, unsigned seed)
+{
+    u32* const ws = (u32*)malloc(4 * LZ_HUF_WS_WORDS);
+    memset(ws, 0x77, 4 * LZ_HUF_WS_WORDS);
+    for (int i = 0; i < count; i++) {
+        HufArgs a;
+        a.stream = (const u8*)src + srcAt[i]; a.n = (u32)ns[i]; a.out = (u8*)out + outAt[i]; a.ws = ws; a.result = 0; a.huffed = 0;
+        lzemu::run_wave(entry_huf, &a, seed + (unsigned)i);
+        sizes[i] = (int)a.result; huffed[i] = (int)a.huffed;
+    }
+    free(ws);
+}
+
 
 // Wave-wide helpers of lz_block.h against scalar definitions on one buffer: forward/backward common lengths
 // (lz_count_fwd, lz_count_back, lz_count_both), lz_copy and the scan/reduce primitives.  Returns the number of
