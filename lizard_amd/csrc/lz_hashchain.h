@@ -107,7 +107,7 @@ LZ_DEV void lz_hc_begin(LzHc& hc, void* slotMem, u32 maxBlock, u32 searchNum)
     hc.wins = (u32*)m;   m += LZ_HC_WINS_BYTES;
     hc.heads = (u32*)m;  m += LZ_HC_HEADS_BYTES(maxBlock);
     hc.hits = (u64*)m;   m += LZ_HC_HITS_BYTES(maxBlock);
-    hc.prev = (u16*)m;   m += 2u * (size_t)maxBlock + 128u;
+    hc.prev = (u16*)m;   m += (2u * (size_t)maxBlock + 128u + 3u) & ~(size_t)3u;     // (an odd maxBlock: chain2 and best stay dword-aligned; the slot's spare 256 bytes pay)
     hc.chain2 = (u32*)m; m += 4u * (size_t)maxBlock + 128u;
     hc.best = (u32*)m;
     hc.searchNum = searchNum;

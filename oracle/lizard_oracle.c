@@ -612,7 +612,8 @@ static int write_stream(int useHuff, const uint8_t* stream, uint32_t n, uint8_t*
     }
     if (*op + 3 + n > oend) return -1;
     wr24(*op, n); *op += 3;
-    memcpy(*op, stream, n); *op += n;
+    if (n) memcpy(*op, stream, n);     /* (an empty stream may have no buffer at all) */
+    *op += n;
     return 0;
 }
 

@@ -30,6 +30,7 @@ extern "C" void emul_stats(unsigned long long* out, int reset)
     for (int i = 0; i < 64; i++) { out[i] = __atomic_load_n(&lzemu_stats[i], __ATOMIC_RELAXED); if (reset) __atomic_store_n(&lzemu_stats[i], 0ull, __ATOMIC_RELAXED); }
 }
 
+#ifndef LZ_EMUL_EXACT_AREAS
 // hashChain levels keep one persistent global slot that is never cleared (as the host library does): whatever an earlier
 // block left in it (bins, links, saved head tables) must not matter.
 static u8* g_hcSlot = nullptr;
@@ -89,6 +90,126 @@ extern "C" int emul_compress_block(const void* src, int n, void* dst, int level,
     free(garbageTable); free(a.tag); free(a.scratch); free(a.hcRegion); free(a.wideOcc);
     return (int)a.result;
 }
+
+#else   /* LZ_EMUL_EXACT_AREAS */
+// -DLZ_EMUL_EXACT_AREAS (tests/emul_asan_main.cpp under AddressSanitizer): every area a kernel body is handed is a heap allocation
+// of its own with exactly the size the product gives it, so that the sanitizer's redzones sit where the neighbouring wave's
+// slice, the next table slot or the next scratch slot begins on the device.  The template arguments, the table kind and the
+// pool / summary / tag sizes are those of the kernel that serves the level (lz_kernels.h), not the roomier ones of the default
+// build above; each size below names the declaration it restates.
+namespace {
+void* exact_area(size_t bytes, int fill)
+{
+    void* p = nullptr;
+    if (posix_memalign(&p, 64, bytes)) abort();              // the start is aligned, the END is exact: nothing is rounded
+    memset(p, fill, bytes);                                  // garbage: the kernel must initialise its state
+    return p;
+}
+struct XArgs { const u8* src; u32 n; u8* dst; u32 level; void* table; u8* ws; u8* scratch; u64* ring; u32 result; u32 tabKind;
+               u32* hufPool; u32 hufPoolMask; u32 hufPoolCount; u32* hcRegion; u32 hcPoolMask; u32 maxBlock; u32* occ; u32 occLog; u32 tagLog; };
+template <int PARSER, int HASHLOG, int AUX, bool HUF>
+void entry_exact(void* a)
+{
+    XArgs* x = (XArgs*)a;
+    LzHufPool hcPool; hcPool.base = x->hcRegion; hcPool.mask = &x->hcPoolMask; hcPool.count = 1; hcPool.stride = LZ_HC_REGION_WORDS;   // a pool of one region
+    u32 r = lz_compress_block<PARSER, HASHLOG, AUX, HUF>(x->src, x->n, x->dst, x->level, x->table, x->ws, x->scratch, x->ring, x->tabKind,
+                                                         x->hufPoolCount ? x->hufPool : nullptr, x->hufPoolCount ? &x->hufPoolMask : nullptr, x->hufPoolCount,
+                                                         &hcPool, x->maxBlock, x->occ, x->occLog, x->tagLog);
+    if (lz_lane() == 0) x->result = r;
+}
+template <int PARSER, int HASHLOG, int AUX>
+void run_exact(bool huf, XArgs* a, unsigned seed) { lzemu::run_wave(huf ? entry_exact<PARSER, HASHLOG, AUX, true> : entry_exact<PARSER, HASHLOG, AUX, false>, a, seed); }
+}  // namespace
+
+// Same contract as the default build's entry.  Which form of a level runs follows the seed as it does there, but only forms that a
+// kernel of lizard_amd/csrc declares are run (levels 22 / 42 have no LDS-table form, level 10 no global-table form).
+extern "C" int emul_compress_block(const void* src, int n, void* dst, int level, unsigned seed)
+{
+    const bool huf = level >= 30;
+    int base = huf ? level - 20 : level;
+    if (level >= 34 && level <= 38) base = level - 21;
+    const bool ncLevel = level == 12 || level == 32 || level == 33;
+    const bool hcLevel = (base >= 13 && base <= 17) || ncLevel;
+    if (!hcLevel && base != 10 && base != 11 && base != 20 && base != 21 && base != 22) return -1;
+    if (n < 1) return -1;
+    XArgs a; memset(&a, 0, sizeof a);
+    a.src = (const u8*)src; a.n = (u32)n; a.dst = (u8*)dst; a.level = (u32)level; a.tagLog = LZ_WIDE_TAGLOG;
+    a.tabKind = LZ_TABKIND_LDS;
+    // per wave, every kernel: Slice::ring[LZ_SEQ_RING] (lz_kernels.h:79) and one scratch slot of LZ_SCRATCH_BYTES (lz_kernels.h:105)
+    a.ring = (u64*)exact_area(8u * LZ_SEQ_RING, 0xEE);
+    a.scratch = (u8*)exact_area(LZ_SCRATCH_BYTES, 0xCC);
+    size_t tableBytes = 0, wsWords = 1;                          // Slice::ws[WSWORDS] (lz_kernels.h:79); WSWORDS = 1 where the wave has no use for it
+    u32 pool = 0;                                                // Huffman workspaces from hufPool[POOL][LZ_HUF_WS_WORDS] (lz_kernels.h:89): one of them here
+    bool occ = false;                                            // wideOcc[..][kOccWords], kOccWords = (2^OCCLOG >> 5) + 1 (lz_kernels.h:94-95)
+    const size_t kWsOwn = LZ_HUF_WS_WORDS, kTags1K = (1u << 10) / 4u;
+    const size_t kPfSlotBytes = 65536u;                          // LZ_PF_SLOT_BYTES (lz_kernels.h:276; that file is device-only)
+    int pfAux = 11;                                              // level 21 / 41: the AUX (TAGLOG) of the form that runs
+    if (hcLevel) {
+        // lz_hashchain_kernel (lz_kernels.h:218): WSWORDS = LZ_HUF_WS_WORDS with the Huffman stage (LZ_HC_HUF_POOL 0), else 1; the table is
+        // the wave's work area: LZ_HC_SLOT_BYTES of the block size rounded up to 64 KiB, without best[] below levels 16 / 37
+        // (lizard_gpu.hip:405-409, :316 needBest), laid out for maxBlock = the launch's block size (lz_kernels.h:128); the chain build
+        // borrows hcPoolMem[..][LZ_HC_REGION_WORDS] (lz_kernels.h:97)
+        const size_t cap = ((size_t)n + 65535u) & ~(size_t)65535u;
+        const bool needBest = base >= 16 && !ncLevel;
+        tableBytes = LZ_HC_SLOT_BYTES(cap) - (needBest ? 0u : 4u * cap);
+        wsWords = huf ? kWsOwn : 1;
+        a.maxBlock = (u32)n;
+        a.hcRegion = (u32*)exact_area(4u * LZ_HC_REGION_WORDS, 0x3C);
+    } else if (base == 10) {
+        // variants/lz_fast12_onewave.h:14-18 (the library itself runs levels 10 / 30 in the split form below).  Level 10: every table
+        // in LDS, WSWORDS 1.  Level 30, by seed: a global-table wave of the mixed form (a 64 KiB slot, lizard_gpu.hip:129 kPf64k; tags
+        // wideTags[..][2^LZ_WIDE_TAGLOG / 4], lz_kernels.h:100-101; pooled workspace), an LDS-table wave of it (WSWORDS 1, pooled
+        // workspace), or the all-LDS form (WSWORDS = LZ_HUF_WS_WORDS).  LDS table: kTabWords = LZ_TAB_BYTES(12) / 4 + 1 (lz_kernels.h:80)
+        tableBytes = 4u * (LZ_TAB_BYTES(12) / 4u + 1u);
+        if (huf && (seed & 1u)) { a.tabKind = LZ_TABKIND_GLOBAL; tableBytes = kPfSlotBytes; wsWords = (1u << LZ_WIDE_TAGLOG) / 4u; pool = 1; }
+        else if (huf && (seed & 3u) == 0u) pool = 1;
+        else if (huf) wsWords = kWsOwn;
+    } else if (base == 11) {
+        // lz_fast18_kernel (lz_kernels.h:199-200): WSWORDS = 2^10 / 4 (the 1 KiB tag array, WIDETAGLOG 10), OCCLOG 16, level 31 a pooled
+        // workspace (LZ_WIDE_HUF_POOL 4); the table slot is LZ_TABWIDE_BYTES(18) (lizard_gpu.hip:129 kWide18)
+        a.tabKind = LZ_TABKIND_GLOBAL; tableBytes = LZ_TABWIDE_BYTES(18); wsWords = kTags1K; a.tagLog = 10; pool = huf; occ = !(seed & 2u);
+    } else if (base == 20) {
+        // lz_fastbig14_kernel (lz_kernels.h:235-236): WSWORDS = 2^10 / 4, OCCLOG 16 (the slot codes), level 40 a pooled workspace; the
+        // table is a 64 KiB slot (lizard_gpu.hip:129 kPf64k, LZ_PF_SLOT_BYTES lz_kernels.h:276)
+        a.tabKind = LZ_TABKIND_GLOBAL; tableBytes = kPfSlotBytes; wsWords = kTags1K; pool = huf; occ = !(seed & 2u);
+    } else if (base == 21) {
+        // lz_pricefast14_kernel (lz_kernels.h:283-288).  SMALL (blocks <= 256 KiB): AUX 10, WSWORDS 1, level 41 a pooled workspace; LDS
+        // tables kTabWords = LZ_TAB24C_BYTES(14) / 4 + 1; the global-table waves' tags wideTags[..][2^AUX / 4] (lz_kernels.h:100-101).
+        // General: AUX 11, WSWORDS = LZ_HUF_WS_WORDS at level 41 (it doubles as the tag array) else 1 and wideTags of 2^11 / 4 words;
+        // LDS tables kTabWords = (4 << 14) / 4 + 1.  Global tables: a 64 KiB slot.
+        const bool small = n <= (1 << 18) && (seed & 3u) != 0u;                   // seed 0 mod 4: the general form at every size
+        if (seed & 1u) { a.tabKind = LZ_TABKIND_GLOBAL; tableBytes = kPfSlotBytes; }
+        else if (small) { a.tabKind = LZ_TABKIND_LDS18; tableBytes = 4u * (LZ_TAB24C_BYTES(14) / 4u + 1u); }
+        else tableBytes = 4u * ((4u << 14) / 4u + 1u);
+        if (small) { wsWords = (seed & 1u) ? kTags1K : 1; pool = huf; }
+        else wsWords = huf ? kWsOwn : (seed & 1u) ? (1u << 11) / 4u : 1;
+        pfAux = small ? 10 : 11;
+    } else {
+        // lz_pricefast18_kernel (lz_kernels.h:297-298): AUX 10, WSWORDS = 2^10 / 4, OCCLOG 16, level 42 a pooled workspace; every table is
+        // a global slot of LZ_TABWIDE_BYTES(18) (lizard_gpu.hip:129 kWide18)
+        a.tabKind = LZ_TABKIND_GLOBAL; tableBytes = LZ_TABWIDE_BYTES(18); wsWords = kTags1K; pool = huf; occ = !(seed & 2u);
+    }
+    a.table = exact_area(tableBytes, hcLevel ? 0xB7 : 0xA5);
+    a.ws = (u8*)exact_area(4u * wsWords, 0x5A);
+    if (pool) { a.hufPool = (u32*)exact_area(4u * LZ_HUF_WS_WORDS, 0x77); a.hufPoolCount = 1; }
+    if (occ) { a.occLog = 16; a.occ = (u32*)exact_area(4u * (((1u << 16) >> 5) + 1u), 0x77); }
+    if (level == 32) run_exact<LZ_PARSER_HASHCHAIN, 14, 6>(true, &a, seed);
+    else if (ncLevel) run_exact<LZ_PARSER_HASHCHAIN, 18, 6>(huf, &a, seed);
+    else switch (base) {
+    case 13: run_exact<LZ_PARSER_HASHCHAIN, 18, 7>(huf, &a, seed); break;
+    case 14: run_exact<LZ_PARSER_HASHCHAIN, 18, 8>(huf, &a, seed); break;
+    case 15: run_exact<LZ_PARSER_HASHCHAIN, 18, 9>(huf, &a, seed); break;
+    case 16: case 17: run_exact<LZ_PARSER_HASHCHAIN, 18, 4>(huf, &a, seed); break;
+    case 10: run_exact<LZ_PARSER_FAST, 12, 0>(huf, &a, seed); break;
+    case 11: run_exact<LZ_PARSER_FAST, 18, 0>(huf, &a, seed); break;
+    case 20: run_exact<LZ_PARSER_FASTBIG, 14, 10>(huf, &a, seed); break;
+    case 21: if (pfAux == 10) run_exact<LZ_PARSER_PRICEFAST, 14, 10>(huf, &a, seed); else run_exact<LZ_PARSER_PRICEFAST, 14, 11>(huf, &a, seed); break;
+    default: run_exact<LZ_PARSER_PRICEFAST, 18, 10>(huf, &a, seed); break;
+    }
+    free(a.ring); free(a.scratch); free(a.table); free(a.ws); free(a.hufPool); free(a.occ); free(a.hcRegion);
+    return (int)a.result;
+}
+#endif  /* LZ_EMUL_EXACT_AREAS */
 
 // One Huffman-candidate stream through lz_put_stream_huf (Lizard_writeStream semantics):
 // out receives LE24 n ‖ LE24 c ‖ payload (accepted) or LE24 n ‖ raw bytes; returns bytes written,
@@ -224,6 +345,15 @@ void entry_split(void* p)
     else if (w->huf)          lz_split_consumer<true>(w->a, w->sh, w->wave - w->a.nProd, w->hufWs);
     else                      lz_split_consumer<false>(w->a, w->sh, w->wave - w->a.nProd, w->hufWs);
 }
+#ifdef LZ_EMUL_EXACT_AREAS
+void entry_split_exact(void* p)
+{
+    SplitWave* w = (SplitWave*)p;
+    if (w->wave < w->a.nProd) { if (w->huf) lz_split_producer<12, false>(w->a, w->sh, w->wave, w->table, w->ring); else lz_split_producer<12, true>(w->a, w->sh, w->wave, w->table, w->ring); }
+    else if (w->huf)          lz_split_consumer<true>(w->a, w->sh, w->wave - w->a.nProd, w->hufWs);
+    else                      lz_split_consumer<false>(w->a, w->sh, w->wave - w->a.nProd, w->hufWs);
+}
+#endif
 }  // namespace
 
 // srcSizes / activeProd: the ragged batches and the producer cap of small launches (LzBatch::srcSizes, ::activeWaves); nullptr / 0 = off
@@ -234,6 +364,7 @@ extern "C" int emul_compress_split(const void* src, int nBlocks, int blockSize, 
 {
     return emul_compress_split_ragged(src, nBlocks, blockSize, lastBlockSize, nullptr, dst, dstStride, sizes, level, nProd, nCons, 0, seed);
 }
+#ifndef LZ_EMUL_EXACT_AREAS
 extern "C" int emul_compress_split_ragged(const void* src, int nBlocks, int blockSize, int lastBlockSize, const unsigned* srcSizes, void* dst,
                                           int dstStride, unsigned* sizes, int level, int nProd, int nCons, int activeProd, unsigned seed)
 {
@@ -268,3 +399,42 @@ extern "C" int emul_compress_split_ragged(const void* src, int nBlocks, int bloc
     free(a.arena);
     return 0;
 }
+#else   /* LZ_EMUL_EXACT_AREAS */
+// The split form with every area exact and on the heap: what lz_fast12_split_kernel declares (lz_kernels.h:165-174) for nProd
+// producers and nCons consumers.  As in the kernel the level-30 producers run without the lane forms (lz_kernels.h:184) and a
+// mailbox has 32 words while they hold every buffer (QN, lz_kernels.h:166).
+extern "C" int emul_compress_split_ragged(const void* src, int nBlocks, int blockSize, int lastBlockSize, const unsigned* srcSizes, void* dst,
+                                          int dstStride, unsigned* sizes, int level, int nProd, int nCons, int activeProd, unsigned seed)
+{
+    const u32 nBufs = 2u + (seed & 1u), qn = (u32)nProd * nBufs <= 32u ? 32u : 64u;
+    if ((level != 10 && level != 30) || nProd < 1 || nCons < 1 || (u32)nProd * nBufs > qn) return -1;
+    const bool huf = level >= 30;
+    LzSplitArgs a;
+    a.src = (const u8*)src; a.blockSize = (u64)blockSize; a.nBlocks = (u32)nBlocks; a.lastBlockSize = (u32)lastBlockSize;
+    a.srcSizes = srcSizes; a.srcOffsets = nullptr; a.activeProd = activeProd > 0 ? (u32)activeProd : 0xFFFFFFFFu;
+    a.dst = (u8*)dst; a.dstStride = (u64)dstStride; a.sizes = sizes; a.level = (u32)level;
+    a.counter = (u32*)exact_area(4, 0);
+    // the workgroup's share of the scratch arena: the kernel claims LZ_SPLIT_ARENA_BYTES of it (static_assert, lz_kernels.h:168)
+    a.arena = (u8*)exact_area(LZ_SPLIT_ARENA_BYTES((size_t)nProd, (size_t)nCons, nBufs), 0xC7);
+    a.nProd = (u32)nProd; a.nCons = (u32)nCons; a.nBufs = nBufs; a.qn = qn;
+    u32* const shared = (u32*)exact_area(4u * LZ_SPLIT_SHARED_WORDS((u32)nProd, (u32)nCons, qn), 0xA5);      // shared[LZ_SPLIT_SHARED_WORDS] (lz_kernels.h:174)
+    const LzSplitShared sh = lz_split_shared(shared, (u32)nProd, (u32)nCons);
+    std::vector<SplitWave> waves((size_t)(nProd + nCons));
+    for (int w = 0; w < nProd + nCons; w++) {
+        SplitWave& x = waves[(size_t)w];
+        x.a = a; x.sh = sh; x.wave = (u32)w; x.huf = huf;
+        // tables[NP][kTabWords], kTabWords = LZ_TAB_BYTES(12) / 4 + 1 (lz_kernels.h:170-171); rings[NP][LZ_SEQ_RING] (:172);
+        // hufWs[NC][LZ_HUF_WS_WORDS], one word each without the Huffman stage (:173)
+        x.table = w < nProd ? exact_area(4u * (LZ_TAB_BYTES(12) / 4u + 1u), 0x5A) : nullptr;
+        x.ring = w < nProd ? (u64*)exact_area(8u * LZ_SEQ_RING, 0xEE) : nullptr;
+        x.hufWs = w >= nProd ? (u32*)exact_area(4u * (huf ? LZ_HUF_WS_WORDS : 1u), 0x77) : nullptr;
+    }
+    lzemu::run_wave(entry_split_init, &waves[0], seed);
+    std::vector<std::thread> th;
+    for (int w = 0; w < nProd + nCons; w++) th.emplace_back([&waves, w, seed] { lzemu::run_wave(entry_split_exact, &waves[(size_t)w], seed * 31u + (unsigned)w + 1u); });
+    for (auto& t : th) t.join();
+    for (SplitWave& x : waves) { free(x.table); free(x.ring); free(x.hufWs); }
+    free(a.arena); free(shared); free(a.counter);
+    return 0;
+}
+#endif  /* LZ_EMUL_EXACT_AREAS */
