@@ -14,7 +14,7 @@
  *   Part 2   batch extension (ours): many independent blocks per call, host- or device-resident, several GPUs, decompression
  *   Part 3   the strict frame twins of rounds 2-3 (LizardGPU_compressFrame ...)
  *   Part 3b  whole-frame decompression on the GPU (LizardGPU_decompressFrame, LizardGPU_decompressFrame_device,
- *            LizardGPU_decompressFrames_device ...)
+ *            LizardGPU_decompressFrames_device, LizardGPU_decompressStream_device ...)
  *
  * Plain C, plain pointers and sizes; no HIP or torch types in any signature (a HIP stream is passed
  * as an opaque void*).
@@ -408,7 +408,12 @@ enum {                                       /* LizardF_errorCodes, lib/lizard_f
 
 /* replaces LizardF_isError, lib/lizard_frame.h:59 / lizard_frame.c:179 */
 unsigned LizardGPU_frameIsError(size_t code);
-/* replaces LizardF_compressFrameBound, lib/lizard_frame.h:122 / lizard_frame.c:229 (same value) */
+/* replaces LizardF_compressFrameBound, lib/lizard_frame.h:122 / lizard_frame.c:229 (same value).
+ * KNOWN SHORTFALL, inherited with the value: the bound counts a last block of ONE byte as one byte of payload, but such a block
+ * makes a record with 6 bytes of payload.  A header without content size is 8 bytes shorter than the 15 the bound allows for, which
+ * hides the 5 missing bytes; with a content size nothing hides them, and a source of 1 byte, or of k * block size + 1 bytes whose
+ * last block is stored as that record, is answered dstMaxSize_tooSmall by every compress entry of Parts 1c and 3 when dst has
+ * exactly the bound.  Give such a frame the bound + 5 bytes (api.compress_stream_device gives every frame 8). */
 size_t LizardGPU_compressFrameBound(size_t srcSize, const LizardGPU_framePrefs_t* preferencesPtr);
 /* replaces LizardF_compressFrame, lib/lizard_frame.h:134 / lizard_frame.c:260 (host buffers, synchronous) */
 size_t LizardGPU_compressFrame(void* dstBuffer, size_t dstMaxSize, const void* srcBuffer, size_t srcSize,
@@ -497,9 +502,10 @@ size_t LizardGPU_compressEnd(LizardGPU_cctx_t* cctx, void* dstBuffer, size_t dst
 
 /* Decodes the ONE frame that starts at src.  Returns the bytes written to dst, or a code LizardGPU_frameIsError() recognises.
  * *srcConsumedPtr (may be NULL) = bytes of src the frame occupied (0 on error): a caller walks concatenated frames by calling
- * again.  A skippable frame decodes to 0 bytes.  dst too small for the frame: dstMaxSize_tooSmall; nothing outside
- * dst[0..dstCapacity) is ever written.  A frame that ends before its end mark / checksum (LizardF_decompress would ask for more
- * input): frameHeader_incomplete when src ends inside the header, GENERIC behind it. */
+ * again (for frames in device memory LizardGPU_decompressStream_device does it in batches).  A skippable frame decodes to 0
+ * bytes.  dst too small for the frame: dstMaxSize_tooSmall; nothing outside dst[0..dstCapacity) is ever written.  A frame that
+ * ends before its end mark / checksum (LizardF_decompress would ask for more input): frameHeader_incomplete when src ends inside
+ * the header, GENERIC behind it. */
 size_t LizardGPU_decompressFrame(void* dst, size_t dstCapacity, const void* src, size_t srcSize, size_t* srcConsumedPtr);
 
 /* Upper bound of what the frame at src decodes to, without decoding: the sum over its block records of (stored raw ? record size
@@ -601,6 +607,45 @@ int LizardGPU_framesInfo_device(size_t nFrames, const void* const* d_srcs, const
  * settled on the device, [2] frames handed to LizardGPU_decompressFrame_device, [3] batch calls that launched anything.
  * 0 or -LIZARDGPU_ERR_*. */
 int LizardGPU_framesDecodeDeviceStats(unsigned long long out[4]);
+
+/* ---- a STREAM of frames in device memory — back to back in one buffer, no table of pointers — decoded into one device buffer ----
+ * What a .liz file is when frames were appended, what `lizard -d` reads, and what a saved state_dict or a file of cache pages is once
+ * it has been loaded into device memory.  The contract is this loop: pos = 0, out = 0; while pos < srcSize, call
+ * LizardGPU_decompressFrame_device(d_dst + out, dstCapacity - out, d_src + pos, srcSize - pos, &used, flags, stream); on an error code
+ * stop; otherwise out += result, pos += used, frames += 1.  The entry answers what the loop answers: the return value is out, or the
+ * first error code; *srcConsumedPtr = pos (on error: the offset of the frame that was refused), *nFramesPtr = the frames completed,
+ * *decodedPtr = out (on error the bytes d_dst[0 .. out) of the completed frames are valid); any of the three may be NULL.
+ * srcSize == 0 returns 0 and touches nothing.  A skippable frame counts as a frame of 0 bytes; LIZARDGPU_FRAME_SKIP_CHECKSUM is
+ * honoured.  SYNCHRONOUS and ordered after what `stream` holds; nothing outside d_src[0 .. srcSize) is read, nothing outside
+ * d_dst[0 .. dstCapacity) is written.  Strict like the rest of Part 3b: no device or a HIP failure is LIZARDGPU_FRAME_ERR_GENERIC
+ * (LizardGPU_lastError has the text).
+ * How: one wave follows the chain of frames on the device (the next frame starts where this one ends: the chain is serial, and no
+ * boundary is ever guessed) in segments of 4 096 frames (LIZARDGPU_STREAM_WALK_FRAMES = 1 .. 2^20 overrides; read at every call),
+ * one host wait per segment that succeeds.  A frame's place in d_dst is the sum of the decoded sizes in front of it, and the header gives a size
+ * when it carries a content size, when the frame is skippable or when it has no records: the longest run of frames in which every
+ * frame but the last has such a size is ONE batch through LizardGPU_decompressFrames_device (two more waits), every frame with its
+ * size as its capacity, the last with the real remainder.  The first frame of the stream that its batch does not answer with exactly
+ * its header's size (a refused frame, a chain the walk refuses, a linked frame of several records) is handed to
+ * LizardGPU_decompressFrame_device with the loop's own arguments, and an error there is the call's answer.
+ * A stream of frames WITH content sizes is one batch, however many frames.  A stream of N frames WITHOUT content sizes is N batches of
+ * one frame: correct, and no faster than the loop.  (The reference's CLI writes no content size by default; its files are normally
+ * one frame, which is one batch.) */
+size_t LizardGPU_decompressStream_device(void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize, size_t* srcConsumedPtr,
+                                         size_t* nFramesPtr, size_t* decodedPtr, unsigned flags, void* stream);
+
+/* The stream walk alone.  For frame k of the stream: its offset, its length, the header's fields and its record count, in HOST arrays
+ * of maxFrames entries (any of the four may be NULL; entries behind maxFrames are not written).  *nFrames = the frames the stream has,
+ * *streamBytes = the bytes they occupy.  0, or -LIZARDGPU_FRAME_ERR_* of the first frame whose chain is refused: *nFrames is the number
+ * of frames in front of it then and *streamBytes its offset (infos[*nFrames] is filled where LizardGPU_frameIndex_device fills *info).
+ * The per-frame values are those of LizardGPU_frameIndex_device called on each frame.  No device or a HIP failure:
+ * -LIZARDGPU_FRAME_ERR_GENERIC.  Synchronous, ordered after what `stream` holds. */
+int LizardGPU_streamIndex_device(const void* d_src, size_t srcSize, uint64_t* frameOffsets, uint64_t* frameBytes, LizardGPU_frameInfo_t* infos,
+                                 size_t* nRecords, size_t maxFrames, size_t* nFrames, size_t* streamBytes, void* stream);
+
+/* LizardGPU_decompressStream_device / LizardGPU_streamIndex_device since process start, selected device: [0] frames answered by a
+ * batch, [1] batches launched, [2] frames this entry handed to LizardGPU_decompressFrame_device (those a batch hands on inside are [2]
+ * of LizardGPU_framesDecodeDeviceStats), [3] stream-walk segments launched.  0 or -LIZARDGPU_ERR_*. */
+int LizardGPU_streamDecodeDeviceStats(unsigned long long out[4]);
 
 #ifdef __cplusplus
 }

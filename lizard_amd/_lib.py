@@ -106,6 +106,13 @@ def lib():
     L.LizardGPU_framesInfo_device.argtypes = [c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
     L.LizardGPU_framesInfo_device.restype = c.c_int
     L.LizardGPU_framesDecodeDeviceStats.argtypes = [c.c_void_p]; L.LizardGPU_framesDecodeDeviceStats.restype = c.c_int
+    L.LizardGPU_decompressStream_device.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint,
+                                                    c.c_void_p]
+    L.LizardGPU_decompressStream_device.restype = c.c_size_t
+    L.LizardGPU_streamIndex_device.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p,
+                                               c.c_void_p, c.c_void_p]
+    L.LizardGPU_streamIndex_device.restype = c.c_int
+    L.LizardGPU_streamDecodeDeviceStats.argtypes = [c.c_void_p]; L.LizardGPU_streamDecodeDeviceStats.restype = c.c_int
     _lib = L
     return L
 

@@ -190,6 +190,11 @@ def compress_frames_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, ch
     tensor i.  No payload crosses PCIe, with or without `checksum`.  One output tensor holds every frame's
     LizardGPU_compressFrameBound-sized region at 256-byte-aligned offsets; returns the list of views region_i[:n_i].  A refused frame
     raises LizardAmdError naming the first such frame's index and error; so does a failure of the machinery."""
+    return _compress_frames_device(tensors, level, block_size_id, checksum, content_size, 0)
+
+
+def _compress_frames_device(tensors, level, block_size_id, checksum, content_size, slack):
+    """compress_frames_device with `slack` bytes of room behind every frame's LizardGPU_compressFrameBound."""
     import torch
     L = _lib.lib()
     tensors = list(tensors)
@@ -206,7 +211,7 @@ def compress_frames_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, ch
     p.frameInfo.contentSize = 1 if content_size else 0          # (non-zero: "write each frame's own size")
     p.compressionLevel = level
     sizes = (ctypes.c_size_t * n)(*[int(t.numel()) for t in tensors])
-    caps = (ctypes.c_size_t * n)(*[_lib.check_frame(L.LizardGPU_compressFrameBound(s, ctypes.byref(p)), "LizardGPU_compressFrameBound") for s in sizes])
+    caps = (ctypes.c_size_t * n)(*[_lib.check_frame(L.LizardGPU_compressFrameBound(s, ctypes.byref(p)), "LizardGPU_compressFrameBound") + slack for s in sizes])
     offsets, total = [], 0
     for cap in caps:
         offsets.append(total)
@@ -403,3 +408,77 @@ def decompress_frames_device(frames, sizes=None, verify_checksum=True):
         if used[i] < src_sizes[i]:
             raise _lib.LizardAmdError(f"LizardGPU_decompressFrames_device: frame {i}: {src_sizes[i] - used[i]} bytes behind the frame's end")
     return [out[o:o + int(r)] for o, r in zip(offsets, results)]
+
+
+STREAM_FRAME_SLACK = 8          # bytes compress_stream_device gives every frame beyond LizardGPU_compressFrameBound (5 are needed)
+
+
+def compress_stream_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksum=False):
+    """A .liz STREAM for `tensors`: compress_frames_device(..., content_size=True) — one frame per tensor, one batch — and one torch.cat
+    of the frame views (torch plumbing, no kernel of its own).  Returns one uint8 CUDA tensor: the frames back to back, which the
+    reference's decoder reads frame after frame and decompress_stream_device decodes in ONE batch, because every header says how
+    many bytes its frame decodes to.
+    Every frame gets STREAM_FRAME_SLACK = 8 bytes of room more than LizardGPU_compressFrameBound (see the note at that function in
+    include/lizard_amd.h): a block of ONE byte makes a record with 6 bytes of payload,
+    5 more than the bound counts.  The 8 bytes a header without content size leaves unused hide that; a 15-byte header does not, so
+    with the bound alone a tensor of one byte — or one whose size is one more than a multiple of the block size — is refused."""
+    import torch
+    frames = _compress_frames_device(tensors, level, block_size_id, checksum, True, STREAM_FRAME_SLACK)
+    if not frames:
+        raise ValueError("compress_stream_device: no tensors")
+    return torch.cat(frames)
+
+
+def stream_info_device(src):
+    """LizardGPU_streamIndex_device: the frames of the stream in `src`, a contiguous uint8 CUDA tensor that holds frames back to back,
+    found by one wave that follows the chain of frames on the device on torch's current stream.  A list with one dict per frame: the
+    keys frames_info_device returns, plus "offset", the frame's place in `src`.  A refused frame raises LizardAmdError naming its
+    index and offset."""
+    import torch
+    L = _lib.lib()
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+    size = int(src.numel())
+    L.LizardGPU_setDevice(src.device.index or 0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
+    room = min(max(size // 8, 1), 1 << 16)                     # (no frame is shorter than 8 bytes)
+    while True:                                                # one walk, unless the stream has more frames than the guess
+        offs, fbytes = (ctypes.c_uint64 * room)(), (ctypes.c_uint64 * room)()
+        infos, nrec = (_FrameInfo * room)(), (ctypes.c_size_t * room)()
+        n, total = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        rc = L.LizardGPU_streamIndex_device(src.data_ptr(), size, offs, fbytes, infos, nrec, room, ctypes.byref(n), ctypes.byref(total), stream)
+        if rc:
+            raise _lib.LizardAmdError(f"LizardGPU_streamIndex_device: frame {n.value} at offset {total.value}: "
+                                      f"{L.LizardF_getErrorName((1 << 64) + rc).decode()} ({L.LizardGPU_lastError().decode()})")
+        if n.value <= room:
+            break
+        room = n.value
+    return [{"block_size_id": f.blockSizeID, "independent": bool(f.blockMode), "checksum": bool(f.contentChecksumFlag),
+             "skippable": bool(f.frameType), "content_size": f.contentSize, "n_records": int(k), "frame_bytes": int(b), "offset": int(o)}
+            for f, k, b, o in zip(infos[:n.value], nrec[:n.value], fbytes[:n.value], offs[:n.value])]
+
+
+def decompress_stream_device(src, dst=None, size=None, verify_checksum=True):
+    """Decode the stream of frames in `src`, a contiguous uint8 CUDA tensor, into one uint8 CUDA tensor on the same device
+    (LizardGPU_decompressStream_device) on torch's current stream: the frames are found on the device and decoded in batches, a stream
+    whose frames carry their content size (compress_stream_device) in ONE batch; neither the frames nor the decoded bytes cross PCIe.
+    Without `dst` the output has `size` bytes, or, without `size`, what one stream_info_device call promises: per frame the content
+    size, else n_records times the frame's block size (an upper bound).  Returns (dst_view, n_frames): the decoded bytes of all
+    frames joined, and how many frames there were.  An error code raises LizardAmdError naming the offset of the refused frame."""
+    import torch
+    L = _lib.lib()
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+    if dst is None:
+        if size is None:
+            size = sum(0 if f["skippable"] else f["content_size"] or f["n_records"] * L.LizardGPU_frameBlockSize(f["block_size_id"])
+                       for f in stream_info_device(src))
+        dst = torch.empty(max(int(size), 1), dtype=torch.uint8, device=src.device)[:int(size)]
+    assert dst.is_cuda and dst.dtype == torch.uint8 and dst.is_contiguous() and dst.device == src.device
+    L.LizardGPU_setDevice(src.device.index or 0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
+    used, frames, decoded = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    r = L.LizardGPU_decompressStream_device(dst.data_ptr(), int(dst.numel()), src.data_ptr(), int(src.numel()), ctypes.byref(used),
+                                            ctypes.byref(frames), ctypes.byref(decoded), 0 if verify_checksum else FRAME_SKIP_CHECKSUM, stream)
+    if L.LizardGPU_frameIsError(r):
+        raise _lib.LizardAmdError(f"LizardGPU_decompressStream_device: frame {frames.value} at offset {used.value}: "
+                                  f"{L.LizardF_getErrorName(r).decode()} ({L.LizardGPU_lastError().decode()})")
+    return dst[:r], frames.value

@@ -23,6 +23,7 @@
 #include "lz_frame_pack.h"     // lz_frame_scan_kernel / lz_frame_gather_kernel: a frame assembled in device memory (LizardGPU_compressFrame_device)
 #include "lz_frames_pack.h"    // the same for a batch of frames, and their checksums (LizardGPU_compressFrames_device)
 #include "unframes_kernels.h"  // a batch of frames walked, decoded and settled in device memory (LizardGPU_decompressFrames_device)
+#include "unstream_kernels.h"  // the walk across the frames of a stream in device memory (LizardGPU_decompressStream_device)
 
 namespace {
 
@@ -887,6 +888,14 @@ int   lzk_unframes_finish_launch(const LzUnframesEntry* d_frames, uint32_t nFram
 {
     if (!d_frames || !d_hashTab || !d_results || nFrames == 0) { snprintf(t_err, sizeof t_err, "bad argument (null pointer or no frames)"); return -LIZARDGPU_ERR_ARG; }
     hipLaunchKernelGGL(lz_unframes_finish_kernel, dim3((nFrames + 255u) / 256u), dim3(256), 0, stream, d_frames, nFrames, d_hashTab, d_results);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
+int   lzk_unstream_walk_launch(const void* d_src, size_t srcSize, LzStreamCtl* d_ctl, struct LzWalkResult* d_res, uint64_t* d_offs, uint32_t tableCap,
+                               hipStream_t stream)
+{
+    if (!d_src || !d_ctl || !d_res || !d_offs || tableCap == 0) { snprintf(t_err, sizeof t_err, "bad argument (null pointer or no table)"); return -LIZARDGPU_ERR_ARG; }
+    hipLaunchKernelGGL(lz_unstream_walk_kernel, dim3(1), dim3(64), 0, stream, (const u8*)d_src, (u64)srcSize, d_ctl, d_res, (u64*)d_offs, tableCap);
     LZ_HIP(hipGetLastError());
     return 0;
 }

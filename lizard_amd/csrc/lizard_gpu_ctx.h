@@ -88,6 +88,7 @@ typedef struct LzCtx {
     unsigned long long devFrameStats[4];  /* LizardGPU_frameDecodeDeviceStats; since process start */
     unsigned long long devFrameCompressStats[4];   /* LizardGPU_frameCompressDeviceStats (lizard_frame_device.c); since process start */
     unsigned long long devFramesDecodeStats[4];    /* LizardGPU_framesDecodeDeviceStats (lizard_unframes_device.c); since process start */
+    unsigned long long devStreamDecodeStats[4];    /* LizardGPU_streamDecodeDeviceStats (lizard_unstream_device.c); since process start */
     LzStage stage[LZ_STAGES];
     LzCombine comb;
     pthread_mutex_t mu;
@@ -187,6 +188,12 @@ int   lzk_unframes_settle_launch(const struct LzUnframesEntry* d_frames, uint32_
                                  LzFramesEntry* d_hashTab, hipStream_t stream);
 int   lzk_unframes_finish_launch(const struct LzUnframesEntry* d_frames, uint32_t nFrames, const LzFramesEntry* d_hashTab,
                                  struct LzUnframesResult* d_results, hipStream_t stream);
+/* LizardGPU_decompressStream_device (lizard_unstream_device.c, unstream_kernels.h): one segment of the walk across the frames of the
+ * stream at d_src, one wave: from d_ctl->pos, frame after frame, each frame's walk result and stream offset into d_res / d_offs
+ * (tableCap entries each), until the stream ends, the table is full or a frame is refused; *d_ctl tells where and why it stopped */
+struct LzStreamCtl;
+int   lzk_unstream_walk_launch(const void* d_src, size_t srcSize, struct LzStreamCtl* d_ctl, struct LzWalkResult* d_res, uint64_t* d_offs,
+                               uint32_t tableCap, hipStream_t stream);
 /* lizard_pipeline_host.c: its staging helpers, shared with lizard_unframe_host.c */
 int    lzp_ensure_dev(LzCtx* c, void** p, size_t* cap, size_t need);
 int    lzp_ensure_pinned(void** p, size_t* cap, size_t need);
