@@ -235,6 +235,25 @@ LZ_DEV void lz_seq_push(LzStreams& st, u32 L, u32 ml, u32 off)
     if constexpr (!LEAN) { st.nflags += 1u; st.nlit += lz_lz4_record_bytes(L, mlc); }
     if ((st.nseq & (LZ_SEQ_RING - 1u)) == 0) lz_seq_flush(st);
 }
+// The level-10 producers (lz_parse_fast<..., LANEFORMS = true>) keep the list's tail in two VGPRs used as a 64-entry table instead of
+// the LDS ring: sequence i of the sub-block waits in lane i & 63 (low word, high word) until its group of 64 is stored.  A push is
+// s_mov m0 + two v_writelane_b32 — no single-lane exec region, no LDS, no branch (the ring's push is an s_and_saveexec region around
+// a ds_write_b64, its flush two LDS syncs and a masked store every 32 sequences).  The list in global memory is the same.
+// the `count` most recent sequences (1..64; they sit in lanes 0..count-1) go to the list: one store
+LZ_DEV void lz_seq_flush_lanes(LzStreams& st, u32 lo, u32 hi, u32 count)
+{
+    if (lz_lane() < count) lz_stq_s(&st.seq[st.nseq - count + lz_lane()], (u64)lo | ((u64)hi << 32));
+    lz_converge();
+}
+template <bool LEAN>
+LZ_DEV void lz_seq_push_lanes(LzStreams& st, u32& lo, u32& hi, u32 L, u32 ml, u32 off)
+{
+    const u32 mlc = ml - 4u;                                     // L | mlc << 18 | off << 36, as two words
+    lz_writelane2(lo, L | (mlc << 18), hi, (mlc >> 14) | (off << 4), st.nseq & 63u);
+    st.nseq += 1u;
+    if constexpr (!LEAN) { st.nflags += 1u; st.nlit += lz_lz4_record_bytes(L, mlc); }
+    if ((st.nseq & 63u) == 0) lz_seq_flush_lanes(st, lo, hi, 64u);          // (all 64 lanes: the compare folds away)
+}
 // nflags / nlit of a finished fastLZ4 sequence list (what lz_seq_push keeps up to date when it is not LEAN): wave-parallel
 LZ_DEV void lz_seq_sizes(LzStreams& st)
 {
@@ -586,6 +605,19 @@ LZ_DEV u32 lz_back_from(u32 cb, u32 P, u32 M, u32 anchor)
 // (Measured in round 5 and not kept, profiles/r05j_m_*: 32 bytes forward in the candidate batch instead of 24 — two more loads per
 //  candidate lane — is 5.3 % SLOWER at level 10 (191.9 vs 202.7 GB/s) although it halves the matches that need a second trip; 16
 //  bytes forward is the same as 24 within 0.3 %.)
+// The tail of a winner round in the LANEFORMS instantiation, two parts that can be built one by one (profiles/producer_tail_ab.txt):
+//   LZ_TAIL_LANES   sequences wait in two VGPRs, not in the LDS ring (lz_seq_push_lanes);
+//   LZ_TAIL_SWEEP   the sweep test stands where lane 0's position moves past an unchecked point (sub-block entry, a round without a
+//                   winner) instead of at the head of every round.
+// (Measured and not kept, same file: ONE uniform test for everything rare behind a winner — an unresolved length, a sweep due inside
+//  the match, the end of the sub-block, a full lane table — with the common path as its fall-through.  Alone -0.5 % as a second copy
+//  of the tail and 0.0 % as two guards around the one tail; together with the two parts above it took back 1.3 of their 2.8 %.)
+#ifndef LZ_TAIL_LANES
+#define LZ_TAIL_LANES 1
+#endif
+#ifndef LZ_TAIL_SWEEP
+#define LZ_TAIL_SWEEP 1
+#endif
 // LZ_STAT(8..12) below count paths for the test emulator (tests/emul); on the device LZ_STAT is empty and what only feeds a mark
 // (`nch`, the second test behind a stale stop, the fourth-round test) is dead code — marked "emulator only" where it stands.
 // LANEFORMS (the level-10 producers): the chain loop's dead set kept per reader and the slot schedule as a recurrence, both below.
@@ -599,6 +631,14 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
     constexpr u32  kW0 = kNarrow ? LZ_WIDE_W0 : 64u;
     constexpr bool kRecur = LANEFORMS && !kNarrow;                        // rounds of 64 slots: the schedule as a recurrence (lz_slot_seed)
     constexpr bool kLaneChain = LANEFORMS && kChain && TAB::kXchg;   // the chain's dead set kept per reader (below)
+    constexpr bool kLaneSeq = LANEFORMS && LZ_TAIL_LANES;             // the list's tail in two VGPRs (lz_seq_push_lanes)
+    // The sweep test away from the head of the round.  The invariant: every live slot stays younger than 2^17 positions, i.e. a sweep
+    // runs no later than kSweepEvery + one round's reach behind the position it fell due at.  Lane 0's position passes an unchecked
+    // point in three ways only.  Sub-block entry: the first round starts at S + 1, tested there.  A round without a winner: the
+    // coming round's lane 0 is tested where the run goes on.  A winner: the sweeps due up to ip = P + ml are made up behind the match,
+    // which leaves ip < sweepAt, and the next round's lane 0 stands at ip - 2 — nothing to test.  (Chained sequences move no round's
+    // lane 0.)  Where inside that slack a sweep runs changes no decision: a slot older than 65535 is dead for the reference either way.
+    constexpr bool kSweepMoved = LANEFORMS && TAB::kSweeps && LZ_TAIL_SWEEP;
     const u32 lane = lz_lane();
     const u64 laneBit = 1ull << lane;
     const u64 lanesBelow = laneBit - 1ull;
@@ -611,6 +651,7 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
     if constexpr (TAB::kSweeps) if (S >= st.sweepAt) { lz_tab_sweep<HASHLOG>(table, S, false); st.sweepAt = S + TAB::kSweepEvery; table.sync(); }
     if (lane == 0) { const u64 b0 = lz_ld64(src + S); table.set(lz_hash5<HASHLOG>(b0), table.entry(S, (u32)b0)); }   // fast.h:66
     table.sync();
+    if constexpr (kSweepMoved) if (S + 1u >= st.sweepAt) { lz_tab_sweep<HASHLOG>(table, S + 1u, false); st.sweepAt = S + 1u + TAB::kSweepEvery; table.sync(); }
 
     u32 ip = S + 1u;        // uniform: run start, or (special==1) the post-match probe position
     u32 special = 0;        // uniform
@@ -627,6 +668,10 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
     if constexpr (kRecur) lz_slot_seed(ip, 0u, lane, pA, sA);
     u32 W = kW0;            // uniform: slots of the round about to run
     u32 v0 = 0;             // uniform: slots consumed by earlier rounds of this run
+    u32 seqLo = 0, seqHi = 0;                                        // kLaneSeq: sequence i of the list waits in lane i & 63
+    const auto push = [&](u32 L, u32 mlen, u32 off) {
+        if constexpr (kLaneSeq) lz_seq_push_lanes<LEAN>(st, seqLo, seqHi, L, mlen, off); else lz_seq_push<LEAN>(st, L, mlen, off);
+    };
     // ONE loop: an iteration is a round of W slots; a round with a winner goes on to extend and push its match and to set up the
     // next run, a round without one moves on inside its run.  (As a loop of rounds inside a loop of runs the two exits of the inner
     // loop, "winner" and "ran into mflimit", were lowered to a state code and a ladder of ~30 scalar instructions and 8 uniform
@@ -647,7 +692,7 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
             pNext = pAhead;
             if (!validNext) pAhead = S;                              // any readable address
         }
-        if constexpr (TAB::kSweeps) {   // keep every live slot younger than 2^17 positions (see LzTab)
+        if constexpr (TAB::kSweeps && !kSweepMoved) {   // keep every live slot younger than 2^17 positions (see LzTab)
             const u32 p0 = lz_readlane(p, 0);
             if (p0 >= st.sweepAt) { lz_tab_sweep<HASHLOG>(table, p0, false); st.sweepAt = p0 + TAB::kSweepEvery; table.sync(); }
         }
@@ -782,7 +827,7 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
                     if (lz_ballot(stale(dead2)) & readers) { LZ_STAT(9); if (lz_ballot(stale(deadMask)) & readers) LZ_STAT(10); break; }   // (inner test: emulator only)
                     deadMask = dead2;
                 }
-                lz_seq_push<LEAN>(st, P - back - anchor, ml + back, P - M);      // fast.h:138
+                push(P - back - anchor, ml + back, P - M);                       // fast.h:138
                 anchor = ipn;
                 commit |= readers; w = w2;
                 if (++nch == 3u) LZ_STAT(8);                                 // emulator only
@@ -822,6 +867,10 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
             v0 += W;
             if (v0 >= 160u && v0 - W < 160u) LZ_STAT(12);                        // emulator only: the run's fourth round comes
             if constexpr (kNarrow) W = W < 32u ? 2u * W : 64u;
+            if constexpr (kSweepMoved) {                                         // the coming round's lane 0 (what the head of that round would test)
+                const u32 p0 = lz_readlane(pNext, 0);
+                if (p0 >= st.sweepAt) { lz_tab_sweep<HASHLOG>(table, p0, false); st.sweepAt = p0 + TAB::kSweepEvery; table.sync(); }
+            }
             continue;
         }
         // ---------------- extend ----------------
@@ -851,12 +900,13 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
         if constexpr (kNarrow) { W = kW0; validNext = validNext && lane < kW0; }
         if (ip > mflimit) validNext = false;                             // (fast.h:143: there is no next run; any readable address)
         nextBytes = lz_ld64(src + (validNext ? pNext : S));
-        lz_seq_push<LEAN>(st, P - anchor, ml, P - M);                    // fast.h:138 (encoded later, in parallel)
+        push(P - anchor, ml, P - M);                                     // fast.h:138 (encoded later, in parallel)
         anchor = ip;
         if (ip > mflimit) break;                                         // fast.h:143
         v0 = 0;
     }
-    if (st.nseq & (LZ_SEQ_RING - 1u)) lz_seq_flush(st);
+    if constexpr (kLaneSeq) { if (st.nseq & 63u) lz_seq_flush_lanes(st, seqLo, seqHi, st.nseq & 63u); }
+    else if (st.nseq & (LZ_SEQ_RING - 1u)) lz_seq_flush(st);
     st.lastLits = E - anchor; st.nlit += E - anchor;                     // fast.h:187-190
     LZ_PROF(st, 3);
 }
