@@ -15,6 +15,8 @@
  *   Part 3   the strict frame twins of rounds 2-3 (LizardGPU_compressFrame ...)
  *   Part 3b  whole-frame decompression on the GPU (LizardGPU_decompressFrame, LizardGPU_decompressFrame_device,
  *            LizardGPU_decompressFrames_device, LizardGPU_decompressStream_device ...)
+ *   Part 3c  tensor streams: element bytes split into planes before compressing (LizardGPU_splitPlanes_device,
+ *            LizardGPU_joinPlanes_device) and the tensor header, a skippable frame (LizardGPU_tensorHeaderWrite / Read)
  *
  * Plain C, plain pointers and sizes; no HIP or torch types in any signature (a HIP stream is passed
  * as an opaque void*).
@@ -646,6 +648,57 @@ int LizardGPU_streamIndex_device(const void* d_src, size_t srcSize, uint64_t* fr
  * batch, [1] batches launched, [2] frames this entry handed to LizardGPU_decompressFrame_device (those a batch hands on inside are [2]
  * of LizardGPU_framesDecodeDeviceStats), [3] stream-walk segments launched.  0 or -LIZARDGPU_ERR_*. */
 int LizardGPU_streamDecodeDeviceStats(unsigned long long out[4]);
+
+/* =====================================================================================================
+ * Part 3c — tensor streams: element bytes split into planes before they are compressed.
+ *
+ * The bytes of a buffer of `size` bytes with element size E in {1, 2, 4, 8}, n = size / E elements, regrouped by significance
+ * (what Blosc calls "shuffle"):  split writes dst[p * n + i] = src[i * E + p] for p < E, i < n and copies the size - n * E tail
+ * bytes to dst + n * E; join is the exact inverse; E = 1 is a copy.  Interleaved, the exponent byte of a float is hidden from a
+ * byte-oriented LZ parser and from huff0; in a plane of its own it has 2.7 bits of entropy for bf16 and fp32 weights.  fp16 gains
+ * nothing at these levels: its top byte holds 5.5 bits and the Huffman stage stores it raw.
+ *
+ * A batch of buffers in ONE launch each way (planes_kernels.h).  d_dsts, d_srcs, sizes, elemSizes: HOST arrays of nBuffers entries;
+ * the pointers are device pointers on the selected device and may have any alignment (the kernels are fastest when both are
+ * 16-byte aligned and n is a multiple of 16).  SYNCHRONOUS and ordered after what `stream` holds.  Nothing outside
+ * d_dsts[i][0 .. sizes[i]) is written, nothing outside d_srcs[i][0 .. sizes[i]) is read.  NOT in place: a dst that overlaps a
+ * src is the caller's error.  An entry of size 0 is allowed and skipped (its pointers may be NULL).
+ * 0, or with NOTHING launched -LIZARDGPU_ERR_ARG: a null array, an elemSizes[i] outside {1, 2, 4, 8}, a null pointer in an entry
+ * of non-zero size, a batch of 2^32 tiles (of 16 KiB) or more.  nBuffers == 0 returns 0 and touches nothing.  Strict like the rest:
+ * no device or a HIP failure is -LIZARDGPU_ERR_* with LizardGPU_lastError set, never a host loop instead. */
+int LizardGPU_splitPlanes_device(size_t nBuffers, void* const* d_dsts, const void* const* d_srcs,
+                                 const size_t* sizes, const uint32_t* elemSizes, void* stream);
+int LizardGPU_joinPlanes_device (size_t nBuffers, void* const* d_dsts, const void* const* d_srcs,
+                                 const size_t* sizes, const uint32_t* elemSizes, void* stream);
+/* Since process start, selected device: [0] buffers split, [1] buffers joined, [2] bytes moved, [3] launches.  0 or -LIZARDGPU_ERR_*. */
+int LizardGPU_planesStats(unsigned long long out[4]);
+
+/* The tensor header: the format has no field that tells a reader which element size a frame's bytes were split with, so a tensor
+ * stream puts a SKIPPABLE frame in front of every data frame.  Every decoder of the format steps over it (the reference's
+ * LizardF_decompress, LizardGPU_decompressStream_device: a frame of 0 bytes that leaves the batch whole).  Its bytes:
+ *     0 ..  3   LE32 magic LIZARDGPU_TENSOR_MAGIC (0x184D2A54, one of the format's sixteen skippable magics)
+ *     4 ..  7   LE32 payload length = 40 + 8 * ndim
+ *   payload:
+ *     0 ..  3   "LZT1"
+ *     4         elemSize: the element size the data frame's bytes were split with, 1 / 2 / 4 / 8 (1 = stored unsplit)
+ *     5         ndim <= 8
+ *     6 ..  7   zero
+ *     8 .. 15   LE64 nbytes: the decoded size of the data frame that follows
+ *    16 .. 39   the dtype's name, zero padded, at least one zero
+ *    40 ..      ndim x LE64 dims
+ * The data frame is an ordinary frame over the SPLIT bytes (LizardGPU_splitPlanes_device's layout for elemSize), so a reader
+ * decodes it with any frame decoder and joins the planes.  Pure host code, no device.
+ * Write: the header's bytes (48 + 8 * ndim), or 0 with nothing written: a null pointer, dstCapacity too small, elemSize not in
+ * {1, 2, 4, 8}, ndim > 8, a dtype without a zero in its 24 bytes.
+ * Read: 0 with *desc and *headerBytes filled (either may be NULL), or -LIZARDGPU_FRAME_ERR_frameType_unknown for anything that
+ * is not such a header — a wrong magic, tag or length, ndim that disagrees with the length or exceeds 8, non-zero pad bytes, an
+ * elemSize not in {1, 2, 4, 8}, a dtype name without a zero inside its field — or -LIZARDGPU_FRAME_ERR_frameHeader_incomplete
+ * when srcSize ends inside the header (every field is judged as soon as the bytes in hand hold it, so a prefix of a valid header
+ * is incomplete, never unknown). */
+typedef struct { uint32_t elemSize; uint32_t ndim; uint64_t nbytes; uint64_t shape[8]; char dtype[24]; } LizardGPU_tensorDesc_t;
+#define LIZARDGPU_TENSOR_MAGIC 0x184D2A54u
+size_t LizardGPU_tensorHeaderWrite(void* dst, size_t dstCapacity, const LizardGPU_tensorDesc_t* desc); /* bytes, or 0 */
+int    LizardGPU_tensorHeaderRead(const void* src, size_t srcSize, LizardGPU_tensorDesc_t* desc, size_t* headerBytes);
 
 #ifdef __cplusplus
 }

@@ -113,6 +113,13 @@ def lib():
                                                c.c_void_p, c.c_void_p]
     L.LizardGPU_streamIndex_device.restype = c.c_int
     L.LizardGPU_streamDecodeDeviceStats.argtypes = [c.c_void_p]; L.LizardGPU_streamDecodeDeviceStats.restype = c.c_int
+    L.LizardGPU_splitPlanes_device.argtypes = [c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+    L.LizardGPU_splitPlanes_device.restype = c.c_int
+    L.LizardGPU_joinPlanes_device.argtypes = [c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+    L.LizardGPU_joinPlanes_device.restype = c.c_int
+    L.LizardGPU_planesStats.argtypes = [c.c_void_p]; L.LizardGPU_planesStats.restype = c.c_int
+    L.LizardGPU_tensorHeaderWrite.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p]; L.LizardGPU_tensorHeaderWrite.restype = c.c_size_t
+    L.LizardGPU_tensorHeaderRead.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]; L.LizardGPU_tensorHeaderRead.restype = c.c_int
     _lib = L
     return L
 

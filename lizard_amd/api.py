@@ -482,3 +482,204 @@ def decompress_stream_device(src, dst=None, size=None, verify_checksum=True):
         raise _lib.LizardAmdError(f"LizardGPU_decompressStream_device: frame {frames.value} at offset {used.value}: "
                                   f"{L.LizardF_getErrorName(r).decode()} ({L.LizardGPU_lastError().decode()})")
     return dst[:r], frames.value
+
+
+# ---- tensor streams: element bytes split into planes before compressing (include/lizard_amd.h Part 3c) ----
+
+TENSOR_HEADER_MAX = 8 + 40 + 8 * 8          # bytes of the longest tensor header (ndim = 8)
+
+
+class _TensorDesc(ctypes.Structure):
+    _fields_ = [("elemSize", ctypes.c_uint32), ("ndim", ctypes.c_uint32), ("nbytes", ctypes.c_uint64), ("shape", ctypes.c_uint64 * 8),
+                ("dtype", ctypes.c_char * 24)]
+
+
+def _as_bytes(t):
+    """The bytes of a contiguous tensor of any dtype and rank as a flat uint8 view."""
+    import torch
+    return t.reshape(-1).view(torch.uint8)
+
+
+def _plane_elem_size(t):
+    """The element size a tensor's bytes are split with: element_size(), the size of one PART for a complex dtype (4 for complex64,
+    8 for complex128), never more than 8."""
+    e = t.element_size()
+    if t.is_complex():
+        e //= 2
+    return min(e, 8)
+
+
+def _planes_device(tensors, elem_sizes, join):
+    import torch
+    L = _lib.lib()
+    tensors = list(tensors)
+    if not tensors:
+        return []
+    device = tensors[0].device
+    for t in tensors:
+        assert t.is_cuda and t.is_contiguous() and t.device == device
+    n = len(tensors)
+    if elem_sizes is None:
+        elem_sizes = [_plane_elem_size(t) for t in tensors]
+    elem_sizes = [int(e) for e in elem_sizes]
+    assert len(elem_sizes) == n
+    sizes = [int(t.numel()) * t.element_size() for t in tensors]
+    offsets, total = [], 0
+    for s in sizes:
+        offsets.append(total)
+        total += (s + 255) & ~255
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=device)
+    srcs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors])
+    dsts = (ctypes.c_void_p * n)(*[out.data_ptr() + o for o in offsets])
+    L.LizardGPU_setDevice(device.index or 0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    fn, name = (L.LizardGPU_joinPlanes_device, "LizardGPU_joinPlanes_device") if join else (L.LizardGPU_splitPlanes_device, "LizardGPU_splitPlanes_device")
+    _lib.check(fn(n, dsts, srcs, (ctypes.c_size_t * n)(*sizes), (ctypes.c_uint32 * n)(*elem_sizes), stream), name)
+    return [out[o:o + s] for o, s in zip(offsets, sizes)]
+
+
+def split_planes_device(tensors, elem_sizes=None):
+    """The bytes of `tensors` — contiguous CUDA tensors of any dtype on one device, taken as bytes — regrouped by significance in ONE
+    launch of LizardGPU_splitPlanes_device on torch's current stream: for a tensor of n elements of E bytes, all byte 0 of every
+    element, then all byte 1, ... (dst[p * n + i] = src[i * E + p]; bytes behind the last whole element are copied).  `elem_sizes`
+    (1, 2, 4 or 8 each) defaults to every tensor's element_size(), the size of one part for a complex dtype (4 for complex64, 8 for
+    complex128).  Returns uint8 views into ONE output tensor, at 256-byte-aligned offsets."""
+    return _planes_device(tensors, elem_sizes, False)
+
+
+def join_planes_device(tensors, elem_sizes):
+    """The inverse of split_planes_device for the same `elem_sizes`, in ONE launch of LizardGPU_joinPlanes_device: uint8 views into one
+    output tensor, at 256-byte-aligned offsets."""
+    return _planes_device(tensors, elem_sizes, True)
+
+
+def compress_tensors_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksum=False, split=True):
+    """A .liz STREAM for `tensors`, contiguous CUDA tensors of any dtype and shape on one device (zero-element ones and scalars
+    allowed), as ONE uint8 CUDA tensor: per tensor a tensor header — a skippable frame with the dtype's name, the shape and the
+    element size of the split (LizardGPU_tensorHeaderWrite) — and one frame with content size over the tensor's bytes SPLIT INTO
+    PLANES.  Every decoder of the format reads the stream (the headers are skipped, the frames decode to the split bytes);
+    decompress_tensors_device gives the tensors back.
+    What the split is for: interleaved, the exponent byte of a float is hidden from a byte-oriented parser and from huff0 — bf16 or
+    fp32 weights come out of compress_stream_device at their own size — and in a plane of its own it has under 3 bits.  fp16 gains
+    nothing at these levels (its top byte holds 5.5 bits and the Huffman stage stores it raw).
+    In this order: one split launch (split_planes_device) for the tensors whose element size is above 1 — none with split=False,
+    which compresses every tensor's own bytes and records element size 1 —, one batch of LizardGPU_compressFrames_device over all
+    tensors, all headers written into one host buffer and uploaded with one copy, one torch.cat.  No payload byte crosses PCIe.
+    Memory: the split bytes are a temporary of the size of the batch (beside the frames' LizardGPU_compressFrameBound regions)."""
+    import torch
+    L = _lib.lib()
+    tensors = list(tensors)
+    if not tensors:
+        raise ValueError("compress_tensors_device: no tensors")
+    device = tensors[0].device
+    descs = []
+    for i, t in enumerate(tensors):
+        assert t.is_cuda and t.is_contiguous() and t.device == device
+        name = str(t.dtype).split(".")[-1].encode()
+        if t.dim() > 8 or len(name) > 23:
+            raise _lib.LizardAmdError(f"compress_tensors_device: tensor {i}: {t.dim()} dimensions / dtype {name.decode()} do not fit a tensor header")
+        d = _TensorDesc()
+        d.elemSize, d.ndim, d.nbytes, d.dtype = (_plane_elem_size(t) if split else 1), t.dim(), int(t.numel()) * t.element_size(), name
+        for k, s in enumerate(t.shape):
+            d.shape[k] = int(s)
+        descs.append(d)
+    raw = [_as_bytes(t) for t in tensors]
+    wide = [i for i, d in enumerate(descs) if d.elemSize > 1]
+    if wide:
+        for i, p in zip(wide, split_planes_device([raw[i] for i in wide], [descs[i].elemSize for i in wide])):
+            raw[i] = p
+    frames = _compress_frames_device(raw, level, block_size_id, checksum, True, STREAM_FRAME_SLACK)
+    host = np.zeros(len(descs) * TENSOR_HEADER_MAX, dtype=np.uint8)
+    at, spans = 0, []
+    for i, d in enumerate(descs):
+        n = L.LizardGPU_tensorHeaderWrite(host.ctypes.data + at, host.size - at, ctypes.byref(d))
+        if not n:
+            raise _lib.LizardAmdError(f"compress_tensors_device: tensor {i}: LizardGPU_tensorHeaderWrite refused the descriptor")
+        spans.append((at, at + n))
+        at += n
+    headers = torch.from_numpy(host[:at]).to(device)
+    return torch.cat([x for (a, b), f in zip(spans, frames) for x in (headers[a:b], f)])
+
+
+def _tensor_stream_index(src, what):
+    """The (tensor header, data frame) pairs of the tensor stream in `src`: one stream_info_device, one indexed read of all header
+    bytes.  [(header frame, data frame, descriptor)]."""
+    import torch
+    L = _lib.lib()
+    frames = stream_info_device(src)
+    pairs, i = [], 0
+    while i < len(frames):
+        k, f = len(pairs), frames[i]
+        if not f["skippable"]:
+            raise _lib.LizardAmdError(f"{what}: tensor {k}: the data frame at offset {f['offset']} has no tensor header in front of it")
+        if i + 1 == len(frames) or frames[i + 1]["skippable"]:
+            raise _lib.LizardAmdError(f"{what}: tensor {k}: the skippable frame at offset {f['offset']} is not followed by a data frame")
+        pairs.append((f, frames[i + 1]))
+        i += 2
+    if not pairs:
+        return []
+    takes = [min(h["frame_bytes"], TENSOR_HEADER_MAX) for h, _ in pairs]
+    index = np.concatenate([np.arange(h["offset"], h["offset"] + n, dtype=np.int64) for (h, _), n in zip(pairs, takes)])
+    host = np.ascontiguousarray(src[torch.from_numpy(index).to(src.device)].cpu().numpy())
+    out, at = [], 0
+    for k, ((h, f), n) in enumerate(zip(pairs, takes)):
+        d, used = _TensorDesc(), ctypes.c_size_t(0)
+        rc = L.LizardGPU_tensorHeaderRead(host.ctypes.data + at, n, ctypes.byref(d), ctypes.byref(used))
+        if rc or used.value != h["frame_bytes"]:
+            raise _lib.LizardAmdError(f"{what}: tensor {k}: the skippable frame at offset {h['offset']} in front of the data frame is not a "
+                                      f"tensor header, so the data frame at offset {f['offset']} has no tensor header in front of it")
+        at += n
+        out.append((h, f, d))
+    return out
+
+
+def tensors_info_device(stream):
+    """What the tensor stream in `stream` (a contiguous uint8 CUDA tensor, what compress_tensors_device returns) holds, without
+    decoding anything: one dict per tensor with dtype (its name), shape, elem_size (of the split; 1 = stored unsplit), nbytes,
+    offset (of the tensor's header in the stream), header_bytes and frame_bytes (of the data frame behind the header).  Raises
+    LizardAmdError naming the tensor's index for a data frame without a tensor header in front of it."""
+    return [{"dtype": d.dtype.decode(), "shape": tuple(int(s) for s in d.shape[:d.ndim]), "elem_size": int(d.elemSize), "nbytes": int(d.nbytes),
+             "offset": h["offset"], "header_bytes": h["frame_bytes"], "frame_bytes": f["frame_bytes"]}
+            for h, f, d in _tensor_stream_index(stream, "tensors_info_device")]
+
+
+def decompress_tensors_device(stream, verify_checksum=True):
+    """The tensors of the tensor stream in `stream`, a contiguous uint8 CUDA tensor (what compress_tensors_device returns), with dtype
+    and shape restored: a list of views into ONE allocation, each 256-byte aligned.  In this order: one stream_info_device, one
+    indexed read of all header bytes, one decompress_stream_device — ONE decode batch for a stream of this library, because the headers
+    are skippable frames and every data frame carries its content size — and one join launch (join_planes_device).  No payload byte
+    crosses PCIe.
+    Raises LizardAmdError naming the index of the offending tensor when a data frame has no tensor header in front of it (or a
+    skippable frame that is none), when a header's nbytes differs from its frame's decoded size (a data frame with records must
+    carry its content size), when the shape does not make nbytes, or when torch does not know the dtype's name; a frame the decoder
+    refuses raises as in decompress_stream_device.
+    Memory: the decoded, still split bytes are a temporary of the size of the batch beside the result."""
+    import torch
+    what = "decompress_tensors_device"
+    entries = _tensor_stream_index(stream, what)
+    if not entries:
+        return []
+    dtypes = []
+    for k, (h, f, d) in enumerate(entries):
+        known = f["content_size"] if f["n_records"] else 0
+        if f["n_records"] and not f["content_size"]:
+            raise _lib.LizardAmdError(f"{what}: tensor {k}: the data frame at offset {f['offset']} carries no content size")
+        if known != d.nbytes:
+            raise _lib.LizardAmdError(f"{what}: tensor {k}: the header says {d.nbytes} bytes, the frame at offset {f['offset']} decodes to {known}")
+        dt = getattr(torch, d.dtype.decode(errors="replace"), None)
+        if not isinstance(dt, torch.dtype):
+            raise _lib.LizardAmdError(f"{what}: tensor {k}: torch knows no dtype {d.dtype.decode(errors='replace')!r}")
+        count = int(np.prod([int(s) for s in d.shape[:d.ndim]], dtype=object)) if d.ndim else 1
+        if count * torch.empty(0, dtype=dt).element_size() != d.nbytes:
+            raise _lib.LizardAmdError(f"{what}: tensor {k}: shape {tuple(d.shape[:d.ndim])} of {d.dtype.decode()} is not {d.nbytes} bytes")
+        dtypes.append(dt)
+    total = sum(int(d.nbytes) for _, _, d in entries)
+    decoded, _ = decompress_stream_device(stream, size=total, verify_checksum=verify_checksum)
+    if int(decoded.numel()) != total:
+        raise _lib.LizardAmdError(f"{what}: the stream decoded to {int(decoded.numel())} bytes, its headers say {total}")
+    pieces, pos = [], 0
+    for _, _, d in entries:
+        pieces.append(decoded[pos:pos + int(d.nbytes)])
+        pos += int(d.nbytes)
+    joined = join_planes_device(pieces, [int(d.elemSize) for _, _, d in entries])
+    return [b.view(dt).reshape(tuple(int(s) for s in d.shape[:d.ndim])) for b, dt, (_, _, d) in zip(joined, dtypes, entries)]

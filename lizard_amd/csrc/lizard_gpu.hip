@@ -24,6 +24,7 @@
 #include "lz_frames_pack.h"    // the same for a batch of frames, and their checksums (LizardGPU_compressFrames_device)
 #include "unframes_kernels.h"  // a batch of frames walked, decoded and settled in device memory (LizardGPU_decompressFrames_device)
 #include "unstream_kernels.h"  // the walk across the frames of a stream in device memory (LizardGPU_decompressStream_device)
+#include "planes_kernels.h"    // the bytes of a batch of buffers split into planes and joined again (LizardGPU_splitPlanes_device)
 
 namespace {
 
@@ -896,6 +897,18 @@ int   lzk_unstream_walk_launch(const void* d_src, size_t srcSize, LzStreamCtl* d
 {
     if (!d_src || !d_ctl || !d_res || !d_offs || tableCap == 0) { snprintf(t_err, sizeof t_err, "bad argument (null pointer or no table)"); return -LIZARDGPU_ERR_ARG; }
     hipLaunchKernelGGL(lz_unstream_walk_kernel, dim3(1), dim3(64), 0, stream, (const u8*)d_src, (u64)srcSize, d_ctl, d_res, (u64*)d_offs, tableCap);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
+int   lzk_planes_launch(LzCtx* c, const LzPlanesEntry* d_tab, uint32_t nEntries, uint32_t nTiles, int join, hipStream_t stream)
+{
+    static_assert(sizeof(LzPlanesEntry) == 32, "the table the host file fills");
+    if (!d_tab || nEntries == 0 || nTiles == 0) { snprintf(t_err, sizeof t_err, "bad argument (null pointer or no tiles)"); return -LIZARDGPU_ERR_ARG; }
+    // a wave per tile up to eight waves per SIMD, a grid stride over the rest
+    const u32 groups = (nTiles + LZP_WAVES - 1u) / LZP_WAVES, cap = (u32)c->cus * 8u;
+    const dim3 grid(groups < cap ? groups : cap), block(64 * LZP_WAVES);
+    if (join) hipLaunchKernelGGL(lz_planes_join_kernel, grid, block, 0, stream, d_tab, nEntries, nTiles);
+    else hipLaunchKernelGGL(lz_planes_split_kernel, grid, block, 0, stream, d_tab, nEntries, nTiles);
     LZ_HIP(hipGetLastError());
     return 0;
 }

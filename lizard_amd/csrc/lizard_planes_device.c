@@ -1,0 +1,178 @@
+/* lizard_planes_device.c — LizardGPU_splitPlanes_device / LizardGPU_joinPlanes_device: the bytes of a batch of device buffers
+ * regrouped by significance, and back, in ONE launch each (planes_kernels.h is the device side), and the tensor header — a
+ * skippable frame that tells a reader of a stream which element size a frame's bytes were split with, and the tensor's dtype and
+ * shape (include/lizard_amd.h Part 3c).  Plain C on the HIP runtime's C API and the shim of lizard_gpu_ctx.h, like the sibling
+ * device entries.
+ *
+ * A call: the arguments are checked before anything is touched; the non-empty buffers become the entries of a table, each with
+ * the number of its first tile (planes_kernels.h); the table goes up from pinned memory and the kernel runs, both on the caller's
+ * stream, behind what it holds; the host waits once.  The table lives in LzCtx::dfTab and stage 0's pinned buffer, like the
+ * tables of the sibling entries: 32 bytes per buffer.  There is no host loop anywhere: no device is an error. */
+#define _POSIX_C_SOURCE 200809L
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "../../include/lizard_amd.h"
+#include "lizard_gpu_ctx.h"
+#include "lizard_gpu_shim.h"
+#include "planes_kernels.h"
+
+#define LZPL_HIP(call)                                                                                 \
+    do {                                                                                               \
+        hipError_t e_ = (call);                                                                        \
+        if (e_ != hipSuccess) {                                                                        \
+            snprintf(lzk_err(), LZK_ERR_BYTES, "%s failed: %s", #call, hipGetErrorString(e_));         \
+            return e_ == hipErrorOutOfMemory ? -LIZARDGPU_ERR_NOMEM : -LIZARDGPU_ERR_HIP;              \
+        }                                                                                              \
+    } while (0)
+
+static int planes_locked(LzCtx* c, const LzPlanesEntry* tab, size_t nEntries, uint32_t nTiles, int join, hipStream_t stream)
+{
+    LzStage* s = c->stage;
+    const size_t bytes = nEntries * sizeof(LzPlanesEntry);
+    int rc;
+    if ((rc = lzk_ctx_init(c))) return rc;
+    if ((rc = lzp_ensure_pinned((void**)&s[0].h_aux, &s[0].h_aux_cap, bytes))) return rc;
+    if ((rc = lzp_ensure_dev(c, (void**)&c->dfTab, &c->dfTabCap, bytes))) return rc;
+    memcpy(s[0].h_aux, tab, bytes);
+    c->hostKernelMs = -1.0f;
+    LZPL_HIP(hipMemcpyAsync(c->dfTab, s[0].h_aux, bytes, hipMemcpyHostToDevice, stream));
+    if ((rc = lzk_planes_launch(c, (const LzPlanesEntry*)c->dfTab, (uint32_t)nEntries, nTiles, join, stream))) return rc;
+    LZPL_HIP(hipStreamSynchronize(stream));
+    return 0;
+}
+
+static int planes(size_t nBuffers, void* const* d_dsts, const void* const* d_srcs, const size_t* sizes, const uint32_t* elemSizes,
+                  int join, hipStream_t stream)
+{
+    LzPlanesEntry* tab;
+    LzGuard g;
+    uint64_t tiles = 0, bytes = 0;
+    size_t i, live = 0;
+    int rc;
+    if (!nBuffers) return 0;
+    lzk_err()[0] = 0;
+    if (!d_dsts || !d_srcs || !sizes || !elemSizes) { snprintf(lzk_err(), LZK_ERR_BYTES, "bad argument (null array)"); return -LIZARDGPU_ERR_ARG; }
+    for (i = 0; i < nBuffers; i++) {
+        const uint32_t E = elemSizes[i];
+        if (E != 1 && E != 2 && E != 4 && E != 8) {
+            snprintf(lzk_err(), LZK_ERR_BYTES, "bad argument (buffer %zu: element size %u is not 1, 2, 4 or 8)", i, (unsigned)E);
+            return -LIZARDGPU_ERR_ARG;
+        }
+        if (!sizes[i]) continue;
+        if (!d_dsts[i] || !d_srcs[i]) { snprintf(lzk_err(), LZK_ERR_BYTES, "bad argument (buffer %zu: null pointer)", i); return -LIZARDGPU_ERR_ARG; }
+        tiles += sizes[i] < E ? 1 : ((uint64_t)(sizes[i] / E) * E + LZP_TILE_BYTES - 1) / LZP_TILE_BYTES;
+        live++;
+    }
+    if (tiles >> 32) { snprintf(lzk_err(), LZK_ERR_BYTES, "bad argument (the batch has 2^32 tiles of %u bytes or more)", LZP_TILE_BYTES); return -LIZARDGPU_ERR_ARG; }
+    if (!live) return 0;                                        /* nothing but empty buffers: nothing to move */
+    if (!(tab = (LzPlanesEntry*)malloc(live * sizeof *tab))) { snprintf(lzk_err(), LZK_ERR_BYTES, "out of host memory"); return -LIZARDGPU_ERR_NOMEM; }
+    for (i = 0, live = 0, tiles = 0; i < nBuffers; i++) {
+        const uint32_t E = elemSizes[i];
+        if (!sizes[i]) continue;
+        tab[live].src = (uint64_t)(uintptr_t)d_srcs[i]; tab[live].dst = (uint64_t)(uintptr_t)d_dsts[i]; tab[live].size = (uint64_t)sizes[i];
+        tab[live].elem = E; tab[live].firstTile = (uint32_t)tiles;
+        tiles += sizes[i] < E ? 1 : ((uint64_t)(sizes[i] / E) * E + LZP_TILE_BYTES - 1) / LZP_TILE_BYTES;
+        bytes += sizes[i];
+        live++;
+    }
+    lzk_guard_acquire(&g);
+    if (g.rc) { free(tab); return g.rc; }
+    rc = planes_locked(g.c, tab, live, (uint32_t)tiles, join, stream);
+    if (rc) {                                                  /* nothing of this call stays in flight; the error text survives */
+        char keep[LZK_ERR_BYTES];
+        memcpy(keep, lzk_err(), sizeof keep);
+        (void)hipStreamSynchronize(stream);
+        (void)hipGetLastError();
+        memcpy(lzk_err(), keep, sizeof keep);
+    } else {
+        g.c->devPlanesStats[join ? 1 : 0] += nBuffers;
+        g.c->devPlanesStats[2] += bytes;
+        g.c->devPlanesStats[3]++;
+    }
+    lzk_guard_release(&g);
+    free(tab);
+    return rc;
+}
+
+int LizardGPU_splitPlanes_device(size_t nBuffers, void* const* d_dsts, const void* const* d_srcs, const size_t* sizes,
+                                 const uint32_t* elemSizes, void* stream)
+{
+    return planes(nBuffers, d_dsts, d_srcs, sizes, elemSizes, 0, (hipStream_t)stream);
+}
+
+int LizardGPU_joinPlanes_device(size_t nBuffers, void* const* d_dsts, const void* const* d_srcs, const size_t* sizes,
+                                const uint32_t* elemSizes, void* stream)
+{
+    return planes(nBuffers, d_dsts, d_srcs, sizes, elemSizes, 1, (hipStream_t)stream);
+}
+
+int LizardGPU_planesStats(unsigned long long out[4])
+{
+    LzCtx* c = lzk_ctx_peek();
+    if (!out) return -LIZARDGPU_ERR_ARG;
+    if (!c) return -LIZARDGPU_ERR_NO_DEVICE;
+    pthread_mutex_lock(&c->mu);
+    memcpy(out, c->devPlanesStats, 4 * sizeof out[0]);
+    pthread_mutex_unlock(&c->mu);
+    return 0;
+}
+
+/* ---- the tensor header: host code, no device ---- */
+#define LZT_FIXED 40                                           /* payload bytes in front of the dims */
+
+static void put_le(uint8_t* p, uint64_t v, int n) { int i; for (i = 0; i < n; i++) p[i] = (uint8_t)(v >> (8 * i)); }
+static uint64_t get_le(const uint8_t* p, int n) { uint64_t v = 0; int i; for (i = 0; i < n; i++) v |= (uint64_t)p[i] << (8 * i); return v; }
+static int elem_ok(uint32_t e) { return e == 1 || e == 2 || e == 4 || e == 8; }
+
+size_t LizardGPU_tensorHeaderWrite(void* dst, size_t dstCapacity, const LizardGPU_tensorDesc_t* desc)
+{
+    uint8_t* p = (uint8_t*)dst;
+    size_t total;
+    uint32_t i;
+    if (!dst || !desc || !elem_ok(desc->elemSize) || desc->ndim > 8 || !memchr(desc->dtype, 0, sizeof desc->dtype)) return 0;
+    total = 8 + LZT_FIXED + 8 * (size_t)desc->ndim;
+    if (dstCapacity < total) return 0;
+    put_le(p, LIZARDGPU_TENSOR_MAGIC, 4);
+    put_le(p + 4, total - 8, 4);
+    memcpy(p + 8, "LZT1", 4);
+    p[12] = (uint8_t)desc->elemSize; p[13] = (uint8_t)desc->ndim; p[14] = p[15] = 0;
+    put_le(p + 16, desc->nbytes, 8);
+    memset(p + 24, 0, 24);
+    memcpy(p + 24, desc->dtype, strlen(desc->dtype));
+    for (i = 0; i < desc->ndim; i++) put_le(p + 8 + LZT_FIXED + 8 * i, desc->shape[i], 8);
+    return total;
+}
+
+int LizardGPU_tensorHeaderRead(const void* src, size_t srcSize, LizardGPU_tensorDesc_t* desc, size_t* headerBytes)
+{
+    const uint8_t* p = (const uint8_t*)src;
+    const int unknown = -(int)LIZARDGPU_FRAME_ERR_frameType_unknown, incomplete = -(int)LIZARDGPU_FRAME_ERR_frameHeader_incomplete;
+    uint64_t len;
+    uint32_t ndim, i;
+    if (headerBytes) *headerBytes = 0;
+    if (!src && srcSize) return -(int)LIZARDGPU_FRAME_ERR_GENERIC;
+    /* every field is judged as soon as the bytes in hand hold it: a prefix of a header is incomplete, never unknown */
+    if (srcSize < 4) return incomplete;
+    if (get_le(p, 4) != LIZARDGPU_TENSOR_MAGIC) return unknown;
+    if (srcSize < 8) return incomplete;
+    len = get_le(p + 4, 4);
+    if (len < LZT_FIXED || len > LZT_FIXED + 64 || (len - LZT_FIXED) % 8) return unknown;
+    ndim = (uint32_t)(len - LZT_FIXED) / 8;
+    if (srcSize >= 12 && memcmp(p + 8, "LZT1", 4)) return unknown;
+    if (srcSize >= 13 && !elem_ok(p[12])) return unknown;
+    if (srcSize >= 14 && p[13] != ndim) return unknown;
+    if (srcSize >= 15 && p[14]) return unknown;
+    if (srcSize >= 16 && p[15]) return unknown;
+    if (srcSize >= 48 && !memchr(p + 24, 0, 24)) return unknown;
+    if (srcSize < 8 + len) return incomplete;
+    if (desc) {
+        memset(desc, 0, sizeof *desc);
+        desc->elemSize = p[12]; desc->ndim = ndim; desc->nbytes = get_le(p + 16, 8);
+        memcpy(desc->dtype, p + 24, 24);
+        for (i = 0; i < ndim; i++) desc->shape[i] = get_le(p + 8 + LZT_FIXED + 8 * i, 8);
+    }
+    if (headerBytes) *headerBytes = (size_t)(8 + len);
+    return 0;
+}
