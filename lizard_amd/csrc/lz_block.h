@@ -566,6 +566,17 @@ LZ_DEV u32 lz_back_from(u32 cb, u32 P, u32 M, u32 anchor)
     const u32 exact = (u32)(roomB <= cb) | ((u32)(M >= 8u) & (u32)(cb < 8u));
     return exact ? (cb < roomB ? cb : roomB) : 0xFFFFu;
 }
+// The same from a lane that prepared its own half beside the batch wait (LANEFORMS, LZ_LATCH_CHAIN): c = the equal bytes when the
+// run ends inside the fetched 8 (0..7: the candidate then starts 8 or more into the block, so only the anchor can cut it shorter),
+// else LZ_BACK_OPEN + the largest room up to which the fetched bytes still decide: 8 when all 8 were equal, 0 when nothing was
+// fetched (a candidate at 0 gives c = 0: no room at all).  r = P - anchor < 2^17.  A minimum, a mask and one compare on scalars.
+// (Candidate at exactly 8 with 8 equal bytes and more room: unresolved here, exact above; lz_count_back gives the same length.)
+#define LZ_BACK_OPEN 0x40000u
+LZ_DEV u32 lz_back_lane(u32 c, u32 r)
+{
+    const u32 b = r < c ? r : c;
+    return b > (c & 15u) ? 0xFFFFu : b;
+}
 
 // Memory-latency structure of a round (the parse is latency-bound: ~70 % of wave time is s_waitcnt):
 //   * the 8 source bytes of every lane are loaded ONE ROUND AHEAD (nextBytes), for the slots the run
@@ -618,6 +629,17 @@ LZ_DEV u32 lz_back_from(u32 cb, u32 P, u32 M, u32 anchor)
 #ifndef LZ_TAIL_SWEEP
 #define LZ_TAIL_SWEEP 1
 #endif
+// The chain pass of the LANEFORMS round (profiles/producer_latch_ab.txt):
+//   LZ_LATCH_CHAIN  the winner's backward length from what its lane prepared beside the batch wait (lz_back_lane: a minimum, a mask
+//                   and one compare on scalars where lz_back_from is 15 scalar instructions), and the exits folded — an unresolved
+//                   length pushes the end lane past 63, `v0 != 0` empties the mask the next winner is taken from, and `ipn > mflimit`
+//                   needs no test at all: lane l1 of a run's first round stands at ipn and is then not valid, so not in okMask.
+// (Measured and not kept, same file: validity carried as the lane mask its compare wrote and `ok` as one compare, -0.8 % alone; one
+//  exit test at the end of the round as two one-sided regions instead of two breaks through the latch, -0.7 % alone although it
+//  takes 13 of the latch's 18 copies away; all three together no better than this part alone.)
+#ifndef LZ_LATCH_CHAIN
+#define LZ_LATCH_CHAIN 1
+#endif
 // LZ_STAT(8..12) below count paths for the test emulator (tests/emul); on the device LZ_STAT is empty and what only feeds a mark
 // (`nch`, the second test behind a stale stop, the fourth-round test) is dead code — marked "emulator only" where it stands.
 // LANEFORMS (the level-10 producers): the chain loop's dead set kept per reader and the slot schedule as a recurrence, both below.
@@ -639,6 +661,7 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
     // which leaves ip < sweepAt, and the next round's lane 0 stands at ip - 2 — nothing to test.  (Chained sequences move no round's
     // lane 0.)  Where inside that slack a sweep runs changes no decision: a slot older than 65535 is dead for the reference either way.
     constexpr bool kSweepMoved = LANEFORMS && TAB::kSweeps && LZ_TAIL_SWEEP;
+    constexpr bool kBackLane = kLaneChain && LZ_LATCH_CHAIN;          // the chain pass on lane-prepared lengths, exits folded
     const u32 lane = lz_lane();
     const u64 laneBit = 1ull << lane;
     const u64 lanesBelow = laneBit - 1ull;
@@ -779,7 +802,8 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
             const u32 common = x ? lz_ctz64(x) >> 3 : y ? 8u + (lz_ctz64(y) >> 3) : (have24 && y2) ? 16u + (lz_ctz64(y2) >> 3) : seen;
             const u32 room = matchlimit - p;                         // p < matchlimit for every valid slot
             if (common < seen || room <= seen) fwd = common < room ? common : room;
-            cbk = !haveBack ? 0u : z ? lz_clz64(z) >> 3 : 8u;        // (lz_back_from turns it into the winner's backward length)
+            if constexpr (kBackLane) cbk = haveBack ? (z ? lz_clz64(z) >> 3 : LZ_BACK_OPEN + 8u) : (ep ? LZ_BACK_OPEN : 0u);   // (for lz_back_lane)
+            else cbk = !haveBack ? 0u : z ? lz_clz64(z) >> 3 : 8u;   // (lz_back_from turns it into the winner's backward length)
         }
         lz_pin(fwd); lz_pin(cbk);                                    // computed here, under this batch's counted wait
         const u64 okMask = lz_ballot(ok);                              // uniform
@@ -794,17 +818,26 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
             w = lz_ctz64(okMask); commit = validMask & (~0ull >> (63u - w));
             // The winner's record is read ONCE per winner: a winner that chains is pushed from it, the last one leaves the loop with
             // it (P, M, ml, back).  The four reads do not depend on each other; lz_back_from is branch-free.
+            // The lanes a chained winner is taken from.  kBackLane: none in a later round of a run (only the first round chains), and the
+            // pass needs no test of ipn: lane l1 of a first round stands at ipn, is not valid when ipn > mflimit, and so is not in okMask.
+            const u64 okNext = (kBackLane && v0) ? 0ull : okMask;
             for (;;) {
                 P = lz_readlane(p, w); M = lz_readlane(ep, w); ml = lz_readlane(fwd, w);
-                back = lz_back_from(lz_readlane(cbk, w), P, M, anchor);
+                if constexpr (kBackLane) back = lz_back_lane(lz_readlane(cbk, w), P - anchor);
+                else back = lz_back_from(lz_readlane(cbk, w), P, M, anchor);
                 if constexpr (!kChain) break;
                 // first round of a run: consecutive positions behind the winner
-                if (v0 != 0 || (ml | back) == 0xFFFFu) break;        // (lengths from the batch are < 32: the OR is 0xFFFF iff one is unresolved)
+                if constexpr (!kBackLane) { if (v0 != 0 || (ml | back) == 0xFFFFu) break; }        // (lengths from the batch are < 32: the OR is 0xFFFF iff one is unresolved)
                 const u32 ipn = P + ml, l1 = w + ml;                 // fast.h:141: ip behind the sequence, and its lane
-                if (ipn > mflimit) break;
-                if (l1 > 63u) { LZ_STAT(11); break; }
+                if constexpr (kBackLane) {
+                    // (an unresolved length is 0xFFFF: either one sends the sum far past 63.  No test of ipn: see okNext above.)
+                    if (l1 + (back >> 4) > 63u) { if (v0 == 0 && (ml | back) != 0xFFFFu && ipn <= mflimit) LZ_STAT(11); break; }   // (inner test: emulator only)
+                } else {
+                    if (ipn > mflimit) break;
+                    if (l1 > 63u) { LZ_STAT(11); break; }
+                }
                 const u64 from1 = ~0ull << l1;
-                const u64 ok2 = okMask & from1;
+                const u64 ok2 = okNext & from1;
                 if (!ok2) break;
                 const u32 w2 = lz_ctz64(ok2);                        // the next accepting lane: probe of ip or a visit of the next run
                 // The lanes inside this match, (w, l1) without l1 - 2 = put(ip-2) (fast.h:146), made puts that never happened.  The
