@@ -28,42 +28,18 @@
 #include "../../include/lizard_amd.h"
 #include "lizard_gpu_ctx.h"
 #include "lizard_gpu_shim.h"
+#include "lizard_device_common.h"
 #include "lizard_xxhash.h"
-
-#define LZ_HIP(call)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            snprintf(lzk_err(), LZK_ERR_BYTES, "%s failed: %s", #call, hipGetErrorString(e_));         \
-            return e_ == hipErrorOutOfMemory ? -LIZARDGPU_ERR_NOMEM : -LIZARDGPU_ERR_HIP;              \
-        }                                                                                              \
-    } while (0)
 
 #ifndef LZC_HASH_PIECE                                       /* (the fake-device tests build with a small odd piece) */
 #define LZC_HASH_PIECE    ((size_t)32 << 20)                 /* source bytes per D2H copy of the checksum pass */
 #endif
-#define LZC_E(code)       ((size_t)-(long)(LIZARDGPU_FRAME_ERR_##code))
-
-size_t   lzgpu_frame_block_size(unsigned blockSizeID);       /* lizard_frame_host.c */
-size_t   lzgpu_frame_write_header(uint8_t* dst, const LizardF_frameInfo_t* frameInfo);
-size_t   lzgpu_frame_device_plan(LizardF_preferences_t* prefs, const LizardF_preferences_t* prefsPtr, const void* d_dst, size_t dstCapacity,
-                                 const void* d_src, size_t srcSize);
 
 /* the small pinned area of a call (stage 0's h_aux): header, the state the cursor starts from, the state read back, end mark + checksum */
 enum { LZC_H_HEADER = 0, LZC_H_INIT = 32, LZC_H_RESULT = 64, LZC_H_TAIL = 96, LZC_H_BYTES = 128 };
 /* a stage's device tables (its d_aux): [64: stage 0 keeps the state here][sizes][offsets] */
 #define LZC_STATE_BYTES 64u
 static size_t c_aux_bytes(size_t P) { return LZC_STATE_BYTES + ((4 * P + 7) & ~(size_t)7) + 8 * (P + 1); }
-
-static size_t chunk_blocks(const LzCtx* c, size_t blockSize)
-{
-    const char* e = getenv("LIZARDGPU_FRAME_CHUNK_BLOCKS");
-    const unsigned long v = e && *e ? strtoul(e, NULL, 10) : 0;
-    size_t n;
-    if (v >= 1 && v <= (1ul << 20)) return (size_t)v;
-    n = lzp_chunk_bytes(c) / blockSize;
-    return n ? n : 1;
-}
 
 typedef struct {
     LzCtx* c;
@@ -88,16 +64,6 @@ static int c_buffers(CJob* j)
         if ((rc = lzp_ensure_dev(c, (void**)&c->stage[s].d_aux, &c->stage[s].d_aux_cap, c_aux_bytes(P)))) return rc;
     }
     j->A = c->stage[0].stream; j->B = c->stage[1].stream; j->C = c->stage[2].stream;
-    return 0;
-}
-
-/* the three streams start behind what the caller's stream holds */
-static int c_order_after(CJob* j, hipStream_t stream)
-{
-    LZ_HIP(hipEventRecord(j->c->stage[0].up, stream));
-    LZ_HIP(hipStreamWaitEvent(j->A, j->c->stage[0].up, 0));
-    LZ_HIP(hipStreamWaitEvent(j->B, j->c->stage[0].up, 0));
-    LZ_HIP(hipStreamWaitEvent(j->C, j->c->stage[0].up, 0));
     return 0;
 }
 
@@ -172,7 +138,7 @@ static int c_finish(CJob* j, int checksumFlag, size_t frameEnd, size_t* result)
         LZ_HIP(hipEventSynchronize(c->stage[0].meta));
         memcpy(st, j->pin + LZC_H_RESULT, sizeof st);
     }
-    if (st[1] || st[0] > (uint64_t)j->limit || j->cap - (size_t)st[0] < frameEnd) { *result = LZC_E(dstMaxSize_tooSmall); return 0; }
+    if (st[1] || st[0] > (uint64_t)j->limit || j->cap - (size_t)st[0] < frameEnd) { *result = LZ_FRAME_E(dstMaxSize_tooSmall); return 0; }
     c_wr32le(j->pin + LZC_H_TAIL, 0);
     if (checksumFlag == 1) { c_wr32le(j->pin + LZC_H_TAIL + 4, Lizard_XXH32_digest(&j->xxh)); tail = 8; }
     LZ_HIP(hipMemcpyAsync(j->dst + (size_t)st[0], j->pin + LZC_H_TAIL, tail, hipMemcpyHostToDevice, j->B));
@@ -181,16 +147,6 @@ static int c_finish(CJob* j, int checksumFlag, size_t frameEnd, size_t* result)
     c->devFrameCompressStats[1] += st[2];
     *result = (size_t)st[0] + tail;
     return 0;
-}
-
-static void c_quiesce(LzCtx* c)                                /* nothing of this call stays in flight; the error text survives */
-{
-    char keep[LZK_ERR_BYTES];
-    int i;
-    memcpy(keep, lzk_err(), sizeof keep);
-    for (i = 0; i < LZ_STAGES; i++) if (c->stage[i].stream) (void)hipStreamSynchronize(c->stage[i].stream);
-    (void)hipGetLastError();
-    memcpy(lzk_err(), keep, sizeof keep);
 }
 
 static size_t c_refuse(size_t code)
@@ -210,7 +166,7 @@ size_t LizardGPU_compressFrame_device(void* d_dst, size_t dstCapacity, const voi
     lzk_err()[0] = 0;
     /* compress_frame, LizardF_compressBegin and LizardF_compressUpdate of lizard_frame_host.c, in their order */
     result = lzgpu_frame_device_plan(&prefs, preferencesPtr, d_dst, dstCapacity, d_src, srcSize);
-    if (result == LZC_E(GENERIC)) { snprintf(lzk_err(), LZK_ERR_BYTES, "bad argument (null pointer)"); return result; }
+    if (result == LZ_FRAME_E(GENERIC)) { snprintf(lzk_err(), LZK_ERR_BYTES, "bad argument (null pointer)"); return result; }
     if (result) return c_refuse(result);
     memset(&j, 0, sizeof j);
     j.blockSize = lzgpu_frame_block_size((unsigned)prefs.frameInfo.blockSizeID);
@@ -220,16 +176,16 @@ size_t LizardGPU_compressFrame_device(void* d_dst, size_t dstCapacity, const voi
     j.src = (const uint8_t*)d_src; j.srcSize = srcSize; j.dst = (uint8_t*)d_dst; j.cap = dstCapacity;
     j.nb = (srcSize + j.blockSize - 1) / j.blockSize;
     j.last = j.nb ? srcSize - (j.nb - 1) * j.blockSize : 0;
-    j.slot = ((size_t)LIZARD_COMPRESSBOUND((int)j.blockSize) + 63) & ~(size_t)63;
+    j.slot = lz_bound_slot(j.blockSize);
     j.limit = dstCapacity - frameEnd;                          /* (the bound counts frameEnd) */
     j.hash = prefs.frameInfo.contentChecksumFlag == 1;
     Lizard_XXH32_reset(&j.xxh, 0);
     lzk_guard_acquire(&g);
-    if (g.rc) return LZC_E(GENERIC);
+    if (g.rc) return LZ_FRAME_E(GENERIC);
     j.c = g.c;
     rc = lzk_ctx_init(g.c);
     if (!rc) {
-        j.perChunk = chunk_blocks(g.c, j.blockSize);
+        j.perChunk = lz_frame_chunk_blocks(g.c, j.blockSize);
         j.nChunks = (j.nb + j.perChunk - 1) / j.perChunk;
         rc = c_buffers(&j);
     }
@@ -239,25 +195,19 @@ size_t LizardGPU_compressFrame_device(void* d_dst, size_t dstCapacity, const voi
         init[0] = (uint64_t)j.headerBytes;
         memcpy(j.pin + LZC_H_INIT, init, sizeof init);
         g.c->hostKernelMs = -1.0f;
-        rc = c_order_after(&j, (hipStream_t)stream);
+        rc = lz_order_after(g.c, (hipStream_t)stream, j.A, j.B, j.C);
     }
     if (!rc) rc = c_enqueue(&j);
     if (!rc) rc = c_hash_source(&j);
     if (!rc) rc = c_finish(&j, (int)prefs.frameInfo.contentChecksumFlag, frameEnd, &result);
-    c_quiesce(g.c);
+    lz_quiesce(g.c);
     lzk_guard_release(&g);
-    if (rc) return LZC_E(GENERIC);
+    if (rc) return LZ_FRAME_E(GENERIC);
     if (LizardGPU_frameIsError(result)) return c_refuse(result);
     return result;
 }
 
 int LizardGPU_frameCompressDeviceStats(unsigned long long out[4])
 {
-    LzCtx* c = lzk_ctx_peek();
-    if (!out) return -LIZARDGPU_ERR_ARG;
-    if (!c) return -LIZARDGPU_ERR_NO_DEVICE;
-    pthread_mutex_lock(&c->mu);
-    memcpy(out, c->devFrameCompressStats, 4 * sizeof out[0]);
-    pthread_mutex_unlock(&c->mu);
-    return 0;
+    return lz_stats_read(out, offsetof(LzCtx, devFrameCompressStats));
 }

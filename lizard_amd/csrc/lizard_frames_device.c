@@ -30,26 +30,10 @@
 #include "../../include/lizard_amd.h"
 #include "lizard_gpu_ctx.h"
 #include "lizard_gpu_shim.h"
-
-#define LZ_HIP(call)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            snprintf(lzk_err(), LZK_ERR_BYTES, "%s failed: %s", #call, hipGetErrorString(e_));         \
-            return e_ == hipErrorOutOfMemory ? -LIZARDGPU_ERR_NOMEM : -LIZARDGPU_ERR_HIP;              \
-        }                                                                                              \
-    } while (0)
-
-#define LZB_E(code)       ((size_t)-(long)(LIZARDGPU_FRAME_ERR_##code))
-
-size_t   lzgpu_frame_block_size(unsigned blockSizeID);       /* lizard_frame_host.c */
-size_t   lzgpu_frame_write_header(uint8_t* dst, const LizardF_frameInfo_t* frameInfo);
-size_t   lzgpu_frame_device_plan(LizardF_preferences_t* prefs, const LizardF_preferences_t* prefsPtr, const void* d_dst, size_t dstCapacity,
-                                 const void* d_src, size_t srcSize);
+#include "lizard_device_common.h"
 
 /* a stage's device tables (its d_aux): the compressed sizes and the record positions of the chunk it holds */
 static size_t b_aux_bytes(size_t P) { return ((4 * P + 7) & ~(size_t)7) + 8 * P; }
-static size_t b_slot(size_t blockSize) { return ((size_t)LIZARD_COMPRESSBOUND((int)blockSize) + 63) & ~(size_t)63; }
 
 typedef struct {
     LzCtx* c;
@@ -68,16 +52,6 @@ typedef struct {
     hipStream_t A, B, C;
 } BJob;
 
-static size_t b_chunk_blocks(const LzCtx* c, size_t blockSize)
-{
-    const char* e = getenv("LIZARDGPU_FRAME_CHUNK_BLOCKS");
-    const unsigned long v = e && *e ? strtoul(e, NULL, 10) : 0;
-    size_t n;
-    if (v >= 1 && v <= (1ul << 20)) return (size_t)v;
-    n = lzp_chunk_bytes(c) / blockSize;
-    return n ? n : 1;
-}
-
 static int b_buffers(BJob* j)
 {
     LzCtx* c = j->c;
@@ -90,7 +64,7 @@ static int b_buffers(BJob* j)
     if ((rc = lzp_ensure_pinned((void**)&c->stage[1].h_aux, &c->stage[1].h_aux_cap, F * sizeof(LzFramesResult)))) return rc;
     if ((rc = lzp_ensure_dev(c, (void**)&c->dfTab, &c->dfTabCap, j->tableBytes + F * sizeof(LzFramesResult)))) return rc;
     for (s = 0; s < LZ_STAGES && s < j->nChunks; s++) {
-        if ((rc = lzp_ensure_dev(c, (void**)&c->stage[s].d_slots, &c->stage[s].d_slots_cap, P * b_slot(j->maxBlock)))) return rc;
+        if ((rc = lzp_ensure_dev(c, (void**)&c->stage[s].d_slots, &c->stage[s].d_slots_cap, P * lz_bound_slot(j->maxBlock)))) return rc;
         if ((rc = lzp_ensure_dev(c, (void**)&c->stage[s].d_aux, &c->stage[s].d_aux_cap, b_aux_bytes(P)))) return rc;
     }
     j->h_frames = (LzFramesEntry*)c->stage[0].h_aux;         j->d_frames = (LzFramesEntry*)c->dfTab;
@@ -163,10 +137,10 @@ static int b_enqueue(BJob* j)
         size_t bs = 0, b;
         for (b = first; b < first + q; b++) if (j->h_frames[j->h_blkFrames[b]].blockSize > bs) bs = j->h_frames[j->h_blkFrames[b]].blockSize;
         if (k >= LZ_STAGES) LZ_HIP(hipStreamWaitEvent(j->A, s->done, 0));      /* the slots and tables are free once chunk k - 3 is gathered */
-        if ((rc = lzk_launch(c, j->base, q, bs, bs, s->d_slots, b_slot(bs), d_sizes, j->level, j->A, s->k0, s->k1, j->d_blkSizes + first,
+        if ((rc = lzk_launch(c, j->base, q, bs, bs, s->d_slots, lz_bound_slot(bs), d_sizes, j->level, j->A, s->k0, s->k1, j->d_blkSizes + first,
                              j->d_blkOffsets + first))) return rc;
         LZ_HIP(hipStreamWaitEvent(j->B, s->k1, 0));
-        if ((rc = lzk_frames_pack_launch(j->base, j->d_blkOffsets + first, j->d_blkSizes + first, j->d_blkFrames + first, s->d_slots, b_slot(bs),
+        if ((rc = lzk_frames_pack_launch(j->base, j->d_blkOffsets + first, j->d_blkSizes + first, j->d_blkFrames + first, s->d_slots, lz_bound_slot(bs),
                                          d_sizes, d_offsets, (uint32_t)q, j->d_frames, j->B))) return rc;
         LZ_HIP(hipEventRecord(s->done, j->B));
         c->devFrameCompressStats[2]++;
@@ -187,7 +161,7 @@ static int b_collect(BJob* j)
     for (i = 0; i < j->nFrames; i++) {
         const LzFramesResult* r = &j->h_results[i];
         if (j->results[i]) continue;
-        if (r->size == LZK_FRAMES_OVERFLOW) { j->results[i] = LZB_E(dstMaxSize_tooSmall); continue; }
+        if (r->size == LZK_FRAMES_OVERFLOW) { j->results[i] = LZ_FRAME_E(dstMaxSize_tooSmall); continue; }
         j->results[i] = (size_t)r->size;
         c->devFrameCompressStats[0] += (unsigned long long)j->h_frames[i].nBlocks - r->rawRecords;
         c->devFrameCompressStats[1] += r->rawRecords;
@@ -195,22 +169,12 @@ static int b_collect(BJob* j)
     return 0;
 }
 
-static void b_quiesce(LzCtx* c)                                /* nothing of this call stays in flight; the error text survives */
-{
-    char keep[LZK_ERR_BYTES];
-    int i;
-    memcpy(keep, lzk_err(), sizeof keep);
-    for (i = 0; i < LZ_STAGES; i++) if (c->stage[i].stream) (void)hipStreamSynchronize(c->stage[i].stream);
-    (void)hipGetLastError();
-    memcpy(lzk_err(), keep, sizeof keep);
-}
-
 static void b_first_refusal(size_t nFrames, const size_t* results)      /* the error text of a call that did its work: the first frame that was refused */
 {
     size_t i;
     for (i = 0; i < nFrames; i++)
         if (LizardGPU_frameIsError(results[i])) {
-            snprintf(lzk_err(), LZK_ERR_BYTES, "frame %zu refused: %s", i, results[i] == LZB_E(GENERIC) ? "bad argument (null pointer)" : LizardF_getErrorName(results[i]));
+            snprintf(lzk_err(), LZK_ERR_BYTES, "frame %zu refused: %s", i, results[i] == LZ_FRAME_E(GENERIC) ? "bad argument (null pointer)" : LizardF_getErrorName(results[i]));
             return;
         }
 }
@@ -249,7 +213,7 @@ int LizardGPU_compressFrames_device(size_t nFrames, void* const* d_dsts, const s
     if (!live) { b_first_refusal(nFrames, results); return 0; }
     if (j.nBlocks > 0xFFFFFFFFu) {
         snprintf(lzk_err(), LZK_ERR_BYTES, "bad argument (more than 2^32 - 1 blocks in one batch)");
-        for (i = 0; i < nFrames; i++) if (!results[i]) results[i] = LZB_E(GENERIC);
+        for (i = 0; i < nFrames; i++) if (!results[i]) results[i] = LZ_FRAME_E(GENERIC);
         return -LIZARDGPU_ERR_ARG;
     }
     lzk_guard_acquire(&g);
@@ -258,7 +222,7 @@ int LizardGPU_compressFrames_device(size_t nFrames, void* const* d_dsts, const s
         j.c = g.c;
         rc = lzk_ctx_init(g.c);
         if (!rc) {
-            j.perChunk = b_chunk_blocks(g.c, j.maxBlock ? j.maxBlock : lzgpu_frame_block_size(1));
+            j.perChunk = lz_frame_chunk_blocks(g.c, j.maxBlock ? j.maxBlock : lzgpu_frame_block_size(1));
             j.nChunks = (j.nBlocks + j.perChunk - 1) / j.perChunk;
             rc = b_buffers(&j);
         }
@@ -269,11 +233,11 @@ int LizardGPU_compressFrames_device(size_t nFrames, void* const* d_dsts, const s
         }
         if (!rc) rc = b_enqueue(&j);
         if (!rc) rc = b_collect(&j);
-        b_quiesce(g.c);
+        lz_quiesce(g.c);
         lzk_guard_release(&g);
     }
     if (rc) {
-        for (i = 0; i < nFrames; i++) if (!results[i] || !LizardGPU_frameIsError(results[i])) results[i] = LZB_E(GENERIC);
+        for (i = 0; i < nFrames; i++) if (!results[i] || !LizardGPU_frameIsError(results[i])) results[i] = LZ_FRAME_E(GENERIC);
         return rc;
     }
     b_first_refusal(nFrames, results);

@@ -511,6 +511,22 @@ int launch(Ctx& c, const void* d_src, size_t nBlocks, size_t blockSize, size_t l
     return rc;
 }
 
+// What the four decode launchers share behind their own argument check and struct fill: the context's own arena (its scratch and
+// counter are shared with the compress launches, ordered by the same events) into the kernel's arguments, one wave per item on a
+// persistent grid of at most one workgroup per CU (lz_decode_grid, lz_kernels.h).
+template <class Batch>
+int launch_decode_grid(Ctx& c, void (*kernel)(Batch), Batch& a, size_t nItems, hipStream_t stream)
+{
+    int rc = ctx_init(c);
+    if (rc) return rc;
+    LzArena& own = c.arena[0];
+    a.scratch = own.scratch; a.counter = own.counter;
+    u32 grid = (u32)((nItems + LZ_WAVES_DEC - 1) / LZ_WAVES_DEC);
+    if (grid > (u32)c.cus) grid = (u32)c.cus;
+    c.hostKernelMs = -1.0f;
+    return enqueue_on(c, own, stream, nullptr, nullptr, [&] { hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * LZ_WAVES_DEC), 0, stream, a); });
+}
+
 int launch_decompress(Ctx& c, const void* d_src, const u64* d_offsets, size_t srcStride, const u32* d_srcSizes, size_t nBlocks,
                       void* d_dst, size_t dstStride, u32* d_outSizes, hipStream_t stream)
 {
@@ -518,21 +534,13 @@ int launch_decompress(Ctx& c, const void* d_src, const u64* d_offsets, size_t sr
         snprintf(t_err, sizeof t_err, "bad argument (null pointer or zero size)");
         return -LIZARDGPU_ERR_ARG;
     }
-    int rc = ctx_init(c);
-    if (rc) return rc;
-    LzArena& own = c.arena[0];                                   // scratch arena and counter are shared with the compress launches
     LzUnBatch a;
     a.src = (const u8*)d_src; a.offsets = d_offsets; a.srcStride = srcStride; a.srcSizes = d_srcSizes;
     a.dst = (u8*)d_dst; a.dstStride = dstStride; a.outSizes = d_outSizes; a.nBlocks = (u32)nBlocks;
-    a.scratch = own.scratch; a.counter = own.counter;
-    u32 grid = (u32)((nBlocks + LZ_WAVES_DEC - 1) / LZ_WAVES_DEC);
-    if (grid > (u32)c.cus) grid = (u32)c.cus;
-    c.hostKernelMs = -1.0f;
-    return enqueue_on(c, own, stream, nullptr, nullptr, [&] { hipLaunchKernelGGL(lz_decompress_kernel, dim3(grid), dim3(64 * LZ_WAVES_DEC), 0, stream, a); });
+    return launch_decode_grid(c, lz_decompress_kernel, a, nBlocks, stream);
 }
 
-// The records of one chunk of a frame (unframe_kernels.h).  Shares the context's own arena and counter with the compress launches
-// and lz_decompress_kernel, ordered by the same events.
+// The records of one chunk of a frame (unframe_kernels.h).
 int launch_unframe(Ctx& c, const void* d_src, const u64* d_payloadOffsets, const u32* d_words, size_t nRecords, void* d_slots,
                    size_t slotBytes, u32* d_outSizes, u32* d_packSizes, hipStream_t stream)
 {
@@ -540,17 +548,10 @@ int launch_unframe(Ctx& c, const void* d_src, const u64* d_payloadOffsets, const
         snprintf(t_err, sizeof t_err, "bad argument (null pointer or zero size)");
         return -LIZARDGPU_ERR_ARG;
     }
-    int rc = ctx_init(c);
-    if (rc) return rc;
-    LzArena& own = c.arena[0];
     LzUnframeBatch a;
     a.src = (const u8*)d_src; a.payloadOffsets = d_payloadOffsets; a.words = d_words;
     a.slots = (u8*)d_slots; a.slotBytes = slotBytes; a.outSizes = d_outSizes; a.packSizes = d_packSizes; a.nRecords = (u32)nRecords;
-    a.scratch = own.scratch; a.counter = own.counter;
-    u32 grid = (u32)((nRecords + LZ_WAVES_DEC - 1) / LZ_WAVES_DEC);
-    if (grid > (u32)c.cus) grid = (u32)c.cus;
-    c.hostKernelMs = -1.0f;
-    return enqueue_on(c, own, stream, nullptr, nullptr, [&] { hipLaunchKernelGGL(lz_unframe_kernel, dim3(grid), dim3(64 * LZ_WAVES_DEC), 0, stream, a); });
+    return launch_decode_grid(c, lz_unframe_kernel, a, nRecords, stream);
 }
 
 // The same with the slots inside the caller's buffer (lz_unframe_inplace_kernel).
@@ -562,17 +563,10 @@ int launch_unframe_inplace(Ctx& c, const void* d_src, const u64* d_payloadOffset
         snprintf(t_err, sizeof t_err, "bad argument (null pointer, zero size or a slot that starts outside the buffer)");
         return -LIZARDGPU_ERR_ARG;
     }
-    int rc = ctx_init(c);
-    if (rc) return rc;
-    LzArena& own = c.arena[0];
     LzUnframeInPlaceBatch a;
     a.src = (const u8*)d_src; a.payloadOffsets = d_payloadOffsets; a.words = d_words;
     a.dst = (u8*)d_dst; a.slotBytes = slotBytes; a.dstRoom = dstRoom; a.outSizes = d_outSizes; a.packSizes = d_packSizes; a.nRecords = (u32)nRecords;
-    a.scratch = own.scratch; a.counter = own.counter;
-    u32 grid = (u32)((nRecords + LZ_WAVES_DEC - 1) / LZ_WAVES_DEC);
-    if (grid > (u32)c.cus) grid = (u32)c.cus;
-    c.hostKernelMs = -1.0f;
-    return enqueue_on(c, own, stream, nullptr, nullptr, [&] { hipLaunchKernelGGL(lz_unframe_inplace_kernel, dim3(grid), dim3(64 * LZ_WAVES_DEC), 0, stream, a); });
+    return launch_decode_grid(c, lz_unframe_inplace_kernel, a, nRecords, stream);
 }
 
 // One segment of the frame walk (unframe_walk.h): one wave, no arena.
@@ -593,7 +587,7 @@ int launch_walk(Ctx& c, const void* d_src, size_t srcSize, size_t startPos, size
     return 0;
 }
 
-// All records of a batch of frames, each decoded in place in its own frame's buffer (unframes_kernels.h).  Arena and counter as above.
+// All records of a batch of frames, each decoded in place in its own frame's buffer (unframes_kernels.h).
 int launch_unframes(Ctx& c, const LzUnframesEntry* d_frames, const u64* d_offs, const u32* d_words, const u32* d_recFrame, u32* d_out,
                     size_t nRecords, hipStream_t stream)
 {
@@ -601,16 +595,9 @@ int launch_unframes(Ctx& c, const LzUnframesEntry* d_frames, const u64* d_offs, 
         snprintf(t_err, sizeof t_err, "bad argument (null pointer or no records)");
         return -LIZARDGPU_ERR_ARG;
     }
-    int rc = ctx_init(c);
-    if (rc) return rc;
-    LzArena& own = c.arena[0];
     LzUnframesBatch a;
     a.frames = d_frames; a.offs = d_offs; a.words = d_words; a.recFrame = d_recFrame; a.out = d_out; a.nRecords = (u32)nRecords;
-    a.scratch = own.scratch; a.counter = own.counter;
-    u32 grid = (u32)((nRecords + LZ_WAVES_DEC - 1) / LZ_WAVES_DEC);
-    if (grid > (u32)c.cus) grid = (u32)c.cus;
-    c.hostKernelMs = -1.0f;
-    return enqueue_on(c, own, stream, nullptr, nullptr, [&] { hipLaunchKernelGGL(lz_unframes_kernel, dim3(grid), dim3(64 * LZ_WAVES_DEC), 0, stream, a); });
+    return launch_decode_grid(c, lz_unframes_kernel, a, nRecords, stream);
 }
 
 }  // namespace

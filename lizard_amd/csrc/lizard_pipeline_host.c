@@ -18,15 +18,7 @@
 #include "../../include/lizard_amd.h"
 #include "lizard_gpu_ctx.h"
 #include "lizard_gpu_shim.h"
-
-#define LZ_HIP(call)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            snprintf(lzk_err(), LZK_ERR_BYTES, "%s failed: %s", #call, hipGetErrorString(e_));         \
-            return e_ == hipErrorOutOfMemory ? -LIZARDGPU_ERR_NOMEM : -LIZARDGPU_ERR_HIP;              \
-        }                                                                                              \
-    } while (0)
+#include "lizard_device_common.h"
 
 static int ensure_dev(LzCtx* c, void** p, size_t* cap, size_t need)
 {
@@ -137,7 +129,7 @@ typedef struct { size_t first, nb, inBytes, packedBytes; int active; } ChunkStat
 
 static int stage_issue(LzCtx* c, LzStage* s, const HostJob* j, ChunkState* ch, int srcPinned, hipEvent_t prevUp)
 {
-    const size_t slot = ((size_t)LIZARD_COMPRESSBOUND((int)j->blockSize) + 63) & ~(size_t)63;
+    const size_t slot = lz_bound_slot(j->blockSize);
     const size_t last = (ch->first + ch->nb == j->nBlocks) ? j->lastBlockSize : j->blockSize;
     const size_t packedCap = ch->nb * (slot + 8);
     const uint8_t* from;
@@ -290,14 +282,7 @@ static int run_host_job_inner(LzCtx* c, const HostJob* j)
 static int run_host_job(LzCtx* c, const HostJob* j)
 {
     const int rc = run_host_job_inner(c, j);
-    if (rc) {                                                   /* a failed chunk may leave copies of the other stages in flight: drain them */
-        char keep[LZK_ERR_BYTES];
-        int i;
-        memcpy(keep, lzk_err(), sizeof keep);
-        for (i = 0; i < LZ_STAGES; i++) if (c->stage[i].stream) (void)hipStreamSynchronize(c->stage[i].stream);
-        (void)hipGetLastError();
-        memcpy(lzk_err(), keep, sizeof keep);
-    }
+    if (rc) lz_quiesce(c);                                      /* a failed chunk may leave copies of the other stages in flight: drain them */
     return rc;
 }
 
@@ -432,7 +417,7 @@ static int batch_on_gpu(LzCtx* c, LzOneJob** jobs, int n, size_t inBytes, size_t
 {
     LzCombine* k = &c->comb;
     LzStage* s = &k->st;
-    const size_t slot = ((size_t)LIZARD_COMPRESSBOUND((int)maxSize) + 63) & ~(size_t)63;
+    const size_t slot = lz_bound_slot(maxSize);
     size_t total;
     int i, rc;
     for (i = 0; i < n; i++) { k->h_srcSizes[i] = (uint32_t)jobs[i]->srcSize; k->h_srcOffsets[i] = jobs[i]->inOff; }
@@ -462,7 +447,7 @@ static int batch_buffers(LzCtx* c, int n, size_t inBytes, size_t maxSize)
 {
     LzCombine* k = &c->comb;
     LzStage* s = &k->st;
-    const size_t slot = ((size_t)LIZARD_COMPRESSBOUND((int)maxSize) + 63) & ~(size_t)63;
+    const size_t slot = lz_bound_slot(maxSize);
     int rc = lzk_ctx_init(c);
     if (rc) return rc;
     if (!s->stream) LZ_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));

@@ -16,16 +16,8 @@
 #include "../../include/lizard_amd.h"
 #include "lizard_gpu_ctx.h"
 #include "lizard_gpu_shim.h"
+#include "lizard_device_common.h"
 #include "planes_kernels.h"
-
-#define LZPL_HIP(call)                                                                                 \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            snprintf(lzk_err(), LZK_ERR_BYTES, "%s failed: %s", #call, hipGetErrorString(e_));         \
-            return e_ == hipErrorOutOfMemory ? -LIZARDGPU_ERR_NOMEM : -LIZARDGPU_ERR_HIP;              \
-        }                                                                                              \
-    } while (0)
 
 static int planes_locked(LzCtx* c, const LzPlanesEntry* tab, size_t nEntries, uint32_t nTiles, int join, hipStream_t stream)
 {
@@ -37,9 +29,9 @@ static int planes_locked(LzCtx* c, const LzPlanesEntry* tab, size_t nEntries, ui
     if ((rc = lzp_ensure_dev(c, (void**)&c->dfTab, &c->dfTabCap, bytes))) return rc;
     memcpy(s[0].h_aux, tab, bytes);
     c->hostKernelMs = -1.0f;
-    LZPL_HIP(hipMemcpyAsync(c->dfTab, s[0].h_aux, bytes, hipMemcpyHostToDevice, stream));
+    LZ_HIP(hipMemcpyAsync(c->dfTab, s[0].h_aux, bytes, hipMemcpyHostToDevice, stream));
     if ((rc = lzk_planes_launch(c, (const LzPlanesEntry*)c->dfTab, (uint32_t)nEntries, nTiles, join, stream))) return rc;
-    LZPL_HIP(hipStreamSynchronize(stream));
+    LZ_HIP(hipStreamSynchronize(stream));
     return 0;
 }
 
@@ -82,10 +74,10 @@ static int planes(size_t nBuffers, void* const* d_dsts, const void* const* d_src
     rc = planes_locked(g.c, tab, live, (uint32_t)tiles, join, stream);
     if (rc) {                                                  /* nothing of this call stays in flight; the error text survives */
         char keep[LZK_ERR_BYTES];
-        memcpy(keep, lzk_err(), sizeof keep);
+        lz_err_save(keep);
         (void)hipStreamSynchronize(stream);
         (void)hipGetLastError();
-        memcpy(lzk_err(), keep, sizeof keep);
+        lz_err_restore(keep);
     } else {
         g.c->devPlanesStats[join ? 1 : 0] += nBuffers;
         g.c->devPlanesStats[2] += bytes;
@@ -110,13 +102,7 @@ int LizardGPU_joinPlanes_device(size_t nBuffers, void* const* d_dsts, const void
 
 int LizardGPU_planesStats(unsigned long long out[4])
 {
-    LzCtx* c = lzk_ctx_peek();
-    if (!out) return -LIZARDGPU_ERR_ARG;
-    if (!c) return -LIZARDGPU_ERR_NO_DEVICE;
-    pthread_mutex_lock(&c->mu);
-    memcpy(out, c->devPlanesStats, 4 * sizeof out[0]);
-    pthread_mutex_unlock(&c->mu);
-    return 0;
+    return lz_stats_read(out, offsetof(LzCtx, devPlanesStats));
 }
 
 /* ---- the tensor header: host code, no device ---- */

@@ -29,17 +29,8 @@
 #include "../../include/lizard_amd.h"
 #include "lizard_gpu_ctx.h"
 #include "lizard_gpu_shim.h"
+#include "lizard_device_common.h"
 #include "lizard_xxhash.h"
-#include "unframe_walk.h"
-
-#define LZ_HIP(call)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            snprintf(lzk_err(), LZK_ERR_BYTES, "%s failed: %s", #call, hipGetErrorString(e_));         \
-            return e_ == hipErrorOutOfMemory ? -LIZARDGPU_ERR_NOMEM : -LIZARDGPU_ERR_HIP;              \
-        }                                                                                              \
-    } while (0)
 
 /* Records per walk segment.  A decode launch has one wave per record and lasts as long as its slowest wave, and the launches of
  * successive segments share the context's arena, so they run one after the other.  Measured with 1 024 records per segment
@@ -53,9 +44,6 @@
 #ifndef LZV_HASH_PIECE                                       /* (the fake-device tests build with a small odd piece) */
 #define LZV_HASH_PIECE    ((size_t)32 << 20)                 /* decoded bytes per D2H copy of the checksum pass */
 #endif
-#define LZV_E(code)       ((size_t)-(long)(LIZARDGPU_FRAME_ERR_##code))
-
-size_t lzgpu_frame_block_size(unsigned blockSizeID);         /* lizard_frame_host.c */
 
 static size_t walk_records(void)
 {
@@ -97,16 +85,6 @@ static int v_buffers(VJob* j)
         j->hres[k] = (LzWalkResult*)h; j->hout[k] = (uint32_t*)(h + 128);
     }
     j->W = c->stage[0].stream; j->D = c->stage[1].stream; j->C = c->stage[2].stream;
-    return 0;
-}
-
-/* the walk streams start behind what the caller's stream holds */
-static int v_order_after(VJob* j, hipStream_t stream)
-{
-    LZ_HIP(hipEventRecord(j->c->stage[0].up, stream));
-    LZ_HIP(hipStreamWaitEvent(j->W, j->c->stage[0].up, 0));
-    LZ_HIP(hipStreamWaitEvent(j->D, j->c->stage[0].up, 0));
-    LZ_HIP(hipStreamWaitEvent(j->C, j->c->stage[0].up, 0));
     return 0;
 }
 
@@ -153,7 +131,7 @@ static int v_hash_to(VJob* j, size_t upto)
 }
 
 /* the caller's buffer cannot take more bytes: a header content size it does hold says the frame, not the buffer, is wrong */
-static size_t v_no_room(const VJob* j) { return j->contentSize && j->cap >= j->contentSize ? LZV_E(frameSize_wrong) : LZV_E(dstMaxSize_tooSmall); }
+static size_t v_no_room(const VJob* j) { return j->contentSize && j->cap >= j->contentSize ? LZ_FRAME_E(frameSize_wrong) : LZ_FRAME_E(dstMaxSize_tooSmall); }
 
 /* The n records of the segment in table set `set`, in order behind dst[0..pos).  0, or -LIZARDGPU_ERR_* for a failure of the
  * machinery; what the FRAME has to say goes to j->pendErr / j->needHost. */
@@ -198,7 +176,7 @@ static int v_decode_segment(VJob* j, int set, size_t n)
             const uint32_t r = out[i + k];
             if (r >= LZV_NEED_HISTORY) {
                 if (r == LZV_NEED_HISTORY && j->linked) j->needHost = 1;
-                else j->pendErr = j->linked ? LZV_E(decompressionFailed) : LZV_E(GENERIC);
+                else j->pendErr = j->linked ? LZ_FRAME_E(decompressionFailed) : LZ_FRAME_E(GENERIC);
                 return 0;
             }
             if (r > j->cap - j->pos - sum) { j->pendErr = v_no_room(j); return 0; }
@@ -232,28 +210,6 @@ static int v_run(VJob* j, unsigned* chainErr)
     }
 }
 
-static void v_info(LizardGPU_frameInfo_t* info, const LzWalkResult* r)
-{
-    memset(info, 0, sizeof *info);
-    info->frameType = (LizardF_frameType_t)r->frameType;
-    info->contentSize = r->contentSize;
-    if (!r->frameType) {
-        info->blockSizeID = (LizardF_blockSizeID_t)r->blockSizeID;
-        info->blockMode = (LizardF_blockMode_t)r->blockMode;
-        info->contentChecksumFlag = (LizardF_contentChecksum_t)r->checksumFlag;
-    }
-}
-
-static void v_quiesce(LzCtx* c)                                /* nothing of this call stays in flight; the error text survives */
-{
-    char keep[LZK_ERR_BYTES];
-    int i;
-    memcpy(keep, lzk_err(), sizeof keep);
-    for (i = 0; i < LZ_STAGES; i++) if (c->stage[i].stream) (void)hipStreamSynchronize(c->stage[i].stream);
-    (void)hipGetLastError();
-    memcpy(lzk_err(), keep, sizeof keep);
-}
-
 /* A linked frame with a block that needs its history: the host twin decodes it from a pinned copy, the result goes back. */
 static size_t v_finish_on_host(const VJob* j, unsigned flags, size_t* consumed)
 {
@@ -266,7 +222,7 @@ static size_t v_finish_on_host(const VJob* j, unsigned flags, size_t* consumed)
         snprintf(lzk_err(), LZK_ERR_BYTES, "pinned copy of a linked frame failed: %s", hipGetErrorString(hipGetLastError()));
         if (hsrc) (void)hipHostFree(hsrc);
         if (hdst) (void)hipHostFree(hdst);
-        return LZV_E(GENERIC);
+        return LZ_FRAME_E(GENERIC);
     }
     if ((flags & LIZARDGPU_FRAME_SKIP_CHECKSUM) && j->checksum) {
         /* the twin always verifies: the copy becomes the same frame without a content checksum (flag cleared, header checksum
@@ -280,7 +236,7 @@ static size_t v_finish_on_host(const VJob* j, unsigned flags, size_t* consumed)
     if (!LizardGPU_frameIsError(r)) {
         if (r && hipMemcpy(j->dst, hdst, r, hipMemcpyHostToDevice) != hipSuccess) {
             snprintf(lzk_err(), LZK_ERR_BYTES, "copy of the host-decoded frame failed: %s", hipGetErrorString(hipGetLastError()));
-            r = LZV_E(GENERIC);
+            r = LZ_FRAME_E(GENERIC);
         } else *consumed = j->frameBytes;
     }
     (void)hipHostFree(hsrc); (void)hipHostFree(hdst);
@@ -298,16 +254,16 @@ size_t LizardGPU_decompressFrame_device(void* d_dst, size_t dstCapacity, const v
     int rc;
     if (srcConsumedPtr) *srcConsumedPtr = 0;
     lzk_err()[0] = 0;
-    if ((!d_dst && dstCapacity) || (!d_src && srcSize)) { snprintf(lzk_err(), LZK_ERR_BYTES, "bad argument (null pointer)"); return LZV_E(GENERIC); }
+    if ((!d_dst && dstCapacity) || (!d_src && srcSize)) { snprintf(lzk_err(), LZK_ERR_BYTES, "bad argument (null pointer)"); return LZ_FRAME_E(GENERIC); }
     memset(&j, 0, sizeof j);
     memset(&first, 0, sizeof first);
     j.src = (const uint8_t*)d_src; j.srcSize = srcSize; j.dst = (uint8_t*)d_dst; j.cap = dstCapacity; j.B = walk_records();
     lzk_guard_acquire(&g);
-    if (g.rc) return LZV_E(GENERIC);
+    if (g.rc) return LZ_FRAME_E(GENERIC);
     j.c = g.c;
     rc = lzk_ctx_init(g.c);
     if (!rc) rc = v_buffers(&j);
-    if (!rc) rc = v_order_after(&j, (hipStream_t)stream);
+    if (!rc) rc = lz_order_after(g.c, (hipStream_t)stream, j.W, j.D, j.C);
     if (!rc) rc = v_issue_walk(&j, 0, 0, j.B, j.B, j.d[0].offs, j.d[0].words);
     if (!rc && hipEventSynchronize(walk_event(&j, 0)) != hipSuccess) { snprintf(lzk_err(), LZK_ERR_BYTES, "the frame walk failed: %s", hipGetErrorString(hipGetLastError())); rc = -LIZARDGPU_ERR_HIP; }
     if (!rc) {
@@ -323,13 +279,13 @@ size_t LizardGPU_decompressFrame_device(void* d_dst, size_t dstCapacity, const v
             rc = v_run(&j, &chainErr);
             if (!rc && !chainErr && !j.pendErr && !j.needHost) {
                 if (hipStreamSynchronize(j.D) != hipSuccess) { snprintf(lzk_err(), LZK_ERR_BYTES, "the frame decode failed: %s", hipGetErrorString(hipGetLastError())); rc = -LIZARDGPU_ERR_HIP; }
-                else if (j.contentSize && (unsigned long long)j.pos != j.contentSize) j.pendErr = LZV_E(frameSize_wrong);
+                else if (j.contentSize && (unsigned long long)j.pos != j.contentSize) j.pendErr = LZ_FRAME_E(frameSize_wrong);
                 else if (j.hash) {
                     uint8_t* q = (uint8_t*)j.hres[0] + sizeof(LzWalkResult);   /* pinned: the head of a host set has room behind the result record */
                     rc = v_hash_to(&j, j.pos);
                     if (!rc && hipMemcpyAsync(q, j.src + j.frameBytes - 4, 4, hipMemcpyDeviceToHost, j.C) == hipSuccess && hipStreamSynchronize(j.C) == hipSuccess) {
                         const uint32_t stored = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
-                        if (stored != Lizard_XXH32_digest(&j.xxh)) j.pendErr = LZV_E(contentChecksum_invalid);
+                        if (stored != Lizard_XXH32_digest(&j.xxh)) j.pendErr = LZ_FRAME_E(contentChecksum_invalid);
                     } else if (!rc) { snprintf(lzk_err(), LZK_ERR_BYTES, "reading the stored checksum failed: %s", hipGetErrorString(hipGetLastError())); rc = -LIZARDGPU_ERR_HIP; }
                 }
                 consumed = j.frameBytes;
@@ -337,9 +293,9 @@ size_t LizardGPU_decompressFrame_device(void* d_dst, size_t dstCapacity, const v
             if (j.needHost && !chainErr && !rc) g.c->devFrameStats[2]++;
         }
     }
-    v_quiesce(g.c);
+    lz_quiesce(g.c);
     lzk_guard_release(&g);
-    if (rc) return LZV_E(GENERIC);
+    if (rc) return LZ_FRAME_E(GENERIC);
     if (chainErr) result = (size_t)-(long)chainErr;
     else if (j.needHost) { consumed = 0; result = v_finish_on_host(&j, flags, &consumed); }
     else if (j.pendErr) result = j.pendErr;
@@ -364,20 +320,21 @@ int LizardGPU_frameIndex_device(const void* d_src, size_t srcSize, LizardGPU_fra
     lzk_err()[0] = 0;
     if (!d_src && srcSize) return -(int)LIZARDGPU_FRAME_ERR_GENERIC;
     memset(&j, 0, sizeof j);
+    memset(&r, 0, sizeof r);
     j.src = (const uint8_t*)d_src; j.srcSize = srcSize; j.B = walk_records();
     lzk_guard_acquire(&g);
     if (g.rc) return -(int)LIZARDGPU_FRAME_ERR_GENERIC;
     j.c = g.c;
     rc = lzk_ctx_init(g.c);
     if (!rc) rc = v_buffers(&j);
-    if (!rc) rc = v_order_after(&j, (hipStream_t)stream);
+    if (!rc) rc = lz_order_after(g.c, (hipStream_t)stream, j.W, j.D, j.C);
     if (!rc) rc = v_issue_walk(&j, 0, 0, (size_t)-1, maxRecords, d_payloadOffsets, d_recordWords);
     if (!rc && hipEventSynchronize(walk_event(&j, 0)) != hipSuccess) { snprintf(lzk_err(), LZK_ERR_BYTES, "the frame walk failed: %s", hipGetErrorString(hipGetLastError())); rc = -LIZARDGPU_ERR_HIP; }
     if (!rc) r = *j.hres[0];
-    v_quiesce(g.c);
+    lz_quiesce(g.c);
     lzk_guard_release(&g);
     if (rc) return -(int)LIZARDGPU_FRAME_ERR_GENERIC;
-    if (info && r.infoValid) v_info(info, &r);
+    if (info && r.infoValid) lz_walk_info(info, &r);
     if (r.status) return -(int)r.status;
     if (nRecords) *nRecords = (size_t)r.nRecords;
     if (frameBytes) *frameBytes = (size_t)r.frameBytes;
@@ -390,11 +347,5 @@ size_t LizardGPU_frameBlockSize(unsigned blockSizeID) { return blockSizeID > 7 ?
 
 int LizardGPU_frameDecodeDeviceStats(unsigned long long out[4])
 {
-    LzCtx* c = lzk_ctx_peek();
-    if (!out) return -LIZARDGPU_ERR_ARG;
-    if (!c) return -LIZARDGPU_ERR_NO_DEVICE;
-    pthread_mutex_lock(&c->mu);
-    memcpy(out, c->devFrameStats, 4 * sizeof out[0]);
-    pthread_mutex_unlock(&c->mu);
-    return 0;
+    return lz_stats_read(out, offsetof(LzCtx, devFrameStats));
 }

@@ -9,15 +9,7 @@
 #include "../../include/lizard_amd.h"
 #include "lizard_gpu_ctx.h"
 #include "lizard_gpu_shim.h"
-
-#define LZ_HIP(call)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            snprintf(lzk_err(), LZK_ERR_BYTES, "%s failed: %s", #call, hipGetErrorString(e_));         \
-            return e_ == hipErrorOutOfMemory ? -LIZARDGPU_ERR_NOMEM : -LIZARDGPU_ERR_HIP;              \
-        }                                                                                              \
-    } while (0)
+#include "lizard_device_common.h"
 #define ensure_dev     lzp_ensure_dev
 #define ensure_pinned  lzp_ensure_pinned
 #define par_memcpy     lzp_par_memcpy
@@ -39,7 +31,6 @@
 
 #define LZU_NEED_HISTORY 0xFFFFFFFEu
 #define LZU_DICT         ((size_t)1 << 24)                  /* LIZARD_DICT_SIZE: no offset reaches further back */
-#define LZU_E(code)      ((size_t)-(long)(LIZARDGPU_FRAME_ERR_##code))
 /* A frame whose blocks lean on their history gains nothing from the device: each such block is decoded twice.  When at least this
  * share of a chunk's records came back as LZD_NEED_HISTORY the rest of the frame goes to the host decoder directly.  The two
  * populations are far apart — measured with the compiled reference on 2 MiB of datagen P50 and text, levels 10 / 17 / 30 / 41,
@@ -50,8 +41,6 @@
  * block that needs history ends the device part, above 1 = never). */
 #define LZU_HOST_SHARE     0.5
 #define LZU_PROBE_RECORDS  64
-
-size_t lzgpu_frame_block_size(unsigned blockSizeID);         /* lizard_frame_host.c */
 
 typedef struct { size_t first, n, spanOff, spanBytes, outBytes; int packed; } UChunk;
 typedef struct {
@@ -136,7 +125,7 @@ static int uf_fetch(UJob* j, LzStage* s, UChunk* ch)
 }
 
 /* the caller's buffer cannot take `n` more bytes: a header content size it does hold says the frame, not the buffer, is wrong */
-static size_t uf_no_room(const UJob* j) { return j->contentSize && j->cap >= j->contentSize ? LZU_E(frameSize_wrong) : LZU_E(dstMaxSize_tooSmall); }
+static size_t uf_no_room(const UJob* j) { return j->contentSize && j->cap >= j->contentSize ? LZ_FRAME_E(frameSize_wrong) : LZ_FRAME_E(dstMaxSize_tooSmall); }
 
 static void uf_hash_to(UJob* j) { if (j->checksum && j->pos > j->hashed) Lizard_XXH32_update(&j->xxh, j->dst + j->hashed, j->pos - j->hashed); j->hashed = j->pos; }
 
@@ -149,12 +138,12 @@ static size_t uf_host_block(UJob* j, size_t rec)
     int r;
     if (room >= j->maxBlock) r = Lizard_decompress_safe_usingDict(payload, (char*)j->dst + j->pos, (int)size, (int)j->maxBlock, (const char*)j->dst + j->pos - d, (int)d);
     else {
-        if (!j->tmp && !(j->tmp = (uint8_t*)malloc(j->maxBlock))) return LZU_E(allocation_failed);
+        if (!j->tmp && !(j->tmp = (uint8_t*)malloc(j->maxBlock))) return LZ_FRAME_E(allocation_failed);
         r = Lizard_decompress_safe_usingDict(payload, (char*)j->tmp, (int)size, (int)j->maxBlock, (const char*)j->dst + j->pos - d, (int)d);
         if (r >= 0 && (size_t)r > room) return uf_no_room(j);
         if (r > 0) memcpy(j->dst + j->pos, j->tmp, (size_t)r);
     }
-    if (r < 0) return j->linked ? LZU_E(decompressionFailed) : LZU_E(GENERIC);
+    if (r < 0) return j->linked ? LZ_FRAME_E(decompressionFailed) : LZ_FRAME_E(GENERIC);
     j->pos += (size_t)r;
     return 0;
 }
@@ -166,13 +155,13 @@ static size_t uf_drain(UJob* j, LzStage* s, UChunk* ch)
     const uint8_t* p = s->h_out;                             /* staging: next good block */
     const uint8_t* runSrc = p; size_t runLen = 0;            /* good blocks are contiguous in staging and in dst: copied run by run */
     size_t i, needHist = 0;
-    if (hipEventSynchronize(s->done) != hipSuccess) { snprintf(lzk_err(), LZK_ERR_BYTES, "hipEventSynchronize failed: %s", hipGetErrorString(hipGetLastError())); return LZU_E(GENERIC); }
+    if (hipEventSynchronize(s->done) != hipSuccess) { snprintf(lzk_err(), LZK_ERR_BYTES, "hipEventSynchronize failed: %s", hipGetErrorString(hipGetLastError())); return LZ_FRAME_E(GENERIC); }
     for (i = 0; i < n; i++) {
         const uint32_t r = out[i];
         const int raw = (j->words[ch->first + i] >> 31) != 0;
         if (r >= LZU_NEED_HISTORY) {
             size_t e;
-            if (r != LZU_NEED_HISTORY || !j->linked) return j->linked ? LZU_E(decompressionFailed) : LZU_E(GENERIC);
+            if (r != LZU_NEED_HISTORY || !j->linked) return j->linked ? LZ_FRAME_E(decompressionFailed) : LZ_FRAME_E(GENERIC);
             if (runLen) { par_memcpy(j->dst + j->pos - runLen, runSrc, runLen); runLen = 0; }
             uf_hash_to(j);
             if ((e = uf_host_block(j, ch->first + i))) return e;
@@ -183,7 +172,7 @@ static size_t uf_drain(UJob* j, LzStage* s, UChunk* ch)
         if (r > j->cap - j->pos) return uf_no_room(j);
         if (!runLen) runSrc = p;
         runLen += r; j->pos += r; p += ch->packed ? r : j->maxBlock;
-        if (!ch->packed && r != j->maxBlock && i + 1 < n) return LZU_E(GENERIC);          /* (uf_fetch packs such a chunk) */
+        if (!ch->packed && r != j->maxBlock && i + 1 < n) return LZ_FRAME_E(GENERIC);          /* (uf_fetch packs such a chunk) */
         j->c->unframeStats[raw ? 1 : 0]++;
     }
     if (runLen) par_memcpy(j->dst + j->pos - runLen, runSrc, runLen);
@@ -199,7 +188,7 @@ static size_t uf_run(UJob* j)
     size_t perChunk = chunk_bytes(c) / j->maxBlock, issued = 0, fetched = 0, drained = 0, nextRec = 0, e;
     int rc;
     if (perChunk == 0) perChunk = 1;
-    if ((rc = lzk_ctx_init(c))) return LZU_E(GENERIC);
+    if ((rc = lzk_ctx_init(c))) return LZ_FRAME_E(GENERIC);
     c->hostKernelMs = -1.0f;
     while (drained < issued || (nextRec < j->nRecords && !j->giveUp)) {
         while (issued - drained < LZ_STAGES && nextRec < j->nRecords && !j->giveUp) {
@@ -209,11 +198,11 @@ static size_t uf_run(UJob* j)
             last = nextRec + n - 1;
             k->first = nextRec; k->n = n; k->spanOff = (size_t)j->off[nextRec];
             k->spanBytes = (size_t)j->off[last] + (j->words[last] & 0x7FFFFFFFu) - k->spanOff;
-            if (uf_issue(j, &c->stage[issued % LZ_STAGES], k, issued ? c->stage[(issued - 1) % LZ_STAGES].up : NULL)) return LZU_E(GENERIC);
+            if (uf_issue(j, &c->stage[issued % LZ_STAGES], k, issued ? c->stage[(issued - 1) % LZ_STAGES].up : NULL)) return LZ_FRAME_E(GENERIC);
             issued++; nextRec += n;
         }
         for (; fetched < issued && fetched < drained + 2; fetched++)
-            if (uf_fetch(j, &c->stage[fetched % LZ_STAGES], &ch[fetched % LZ_STAGES])) return LZU_E(GENERIC);
+            if (uf_fetch(j, &c->stage[fetched % LZ_STAGES], &ch[fetched % LZ_STAGES])) return LZ_FRAME_E(GENERIC);
         if ((e = uf_drain(j, &c->stage[drained % LZ_STAGES], &ch[drained % LZ_STAGES]))) return e;
         drained++;
         if (j->giveUp) { nextRec = ch[(drained - 1) % LZ_STAGES].first + ch[(drained - 1) % LZ_STAGES].n; break; }
@@ -241,10 +230,10 @@ size_t LizardGPU_decompressFrame(void* dst, size_t dstCapacity, const void* src,
     LzGuard g;
     uint64_t* off = NULL; uint32_t* words = NULL;
     size_t n = 0, frameBytes = 0, result;
-    int rc, i;
+    int rc;
     if (srcConsumedPtr) *srcConsumedPtr = 0;
     lzk_err()[0] = 0;
-    if ((!dst && dstCapacity) || (!src && srcSize)) { snprintf(lzk_err(), LZK_ERR_BYTES, "bad argument (null pointer)"); return LZU_E(GENERIC); }
+    if ((!dst && dstCapacity) || (!src && srcSize)) { snprintf(lzk_err(), LZK_ERR_BYTES, "bad argument (null pointer)"); return LZ_FRAME_E(GENERIC); }
     if ((rc = LizardGPU_frameIndex(src, srcSize, &info, NULL, NULL, 0, &n, &frameBytes))) {
         snprintf(lzk_err(), LZK_ERR_BYTES, "frame refused: %s", LizardF_getErrorName((size_t)(long)rc));
         return (size_t)(long)rc;
@@ -258,32 +247,27 @@ size_t LizardGPU_decompressFrame(void* dst, size_t dstCapacity, const void* src,
         if (n) {
             const char* e = getenv("LIZARDGPU_UNFRAME_HOST_SHARE");
             off = (uint64_t*)malloc(n * sizeof *off); words = (uint32_t*)malloc(n * sizeof *words);
-            if (!off || !words) { free(off); free(words); snprintf(lzk_err(), LZK_ERR_BYTES, "out of host memory"); return LZU_E(allocation_failed); }
+            if (!off || !words) { free(off); free(words); snprintf(lzk_err(), LZK_ERR_BYTES, "out of host memory"); return LZ_FRAME_E(allocation_failed); }
             (void)LizardGPU_frameIndex(src, srcSize, &info, off, words, n, &n, &frameBytes);
             j.off = off; j.words = words; j.nRecords = n;
             j.maxBlock = lzgpu_frame_block_size((unsigned)info.blockSizeID);
             j.hostShare = e && *e ? strtod(e, NULL) : LZU_HOST_SHARE;
             lzk_guard_acquire(&g);
-            if (g.rc) result = LZU_E(GENERIC);
+            if (g.rc) result = LZ_FRAME_E(GENERIC);
             else {
-                char keep[LZK_ERR_BYTES];
                 j.c = g.c;
                 j.srcPinned = is_pinned_host(src);
                 result = uf_run(&j);
-                /* copies of chunks that were not finished (an error, or the hand-over to the host decoder) may still be in flight */
-                memcpy(keep, lzk_err(), sizeof keep);
-                for (i = 0; i < LZ_STAGES; i++) if (g.c->stage[i].stream) (void)hipStreamSynchronize(g.c->stage[i].stream);
-                (void)hipGetLastError();
-                memcpy(lzk_err(), keep, sizeof keep);
+                lz_quiesce(g.c);                               /* copies of chunks that were not finished (an error, or the hand-over to the host decoder) may still be in flight */
                 lzk_guard_release(&g);
             }
             free(j.tmp); free(off); free(words);
         }
-        if (!result && j.contentSize && (unsigned long long)j.pos != j.contentSize) result = LZU_E(frameSize_wrong);
+        if (!result && j.contentSize && (unsigned long long)j.pos != j.contentSize) result = LZ_FRAME_E(frameSize_wrong);
         if (!result && j.checksum) {
             const uint8_t* q = (const uint8_t*)src + frameBytes - 4;
             const uint32_t stored = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
-            if (stored != Lizard_XXH32_digest(&j.xxh)) result = LZU_E(contentChecksum_invalid);
+            if (stored != Lizard_XXH32_digest(&j.xxh)) result = LZ_FRAME_E(contentChecksum_invalid);
         }
         if (result) {
             if (!lzk_err()[0]) snprintf(lzk_err(), LZK_ERR_BYTES, "frame refused: %s", LizardF_getErrorName(result));
@@ -296,13 +280,7 @@ size_t LizardGPU_decompressFrame(void* dst, size_t dstCapacity, const void* src,
 
 int LizardGPU_frameDecodeStats(unsigned long long out[4])
 {
-    LzCtx* c = lzk_ctx_peek();
-    if (!out) return -LIZARDGPU_ERR_ARG;
-    if (!c) return -LIZARDGPU_ERR_NO_DEVICE;
-    pthread_mutex_lock(&c->mu);
-    memcpy(out, c->unframeStats, 4 * sizeof out[0]);
-    pthread_mutex_unlock(&c->mu);
-    return 0;
+    return lz_stats_read(out, offsetof(LzCtx, unframeStats));    /* (the first four of five: LizardGPU_frameDecodePackedChunks has the fifth) */
 }
 
 unsigned long long LizardGPU_frameDecodePackedChunks(void)

@@ -31,20 +31,8 @@
 #include "../../include/lizard_amd.h"
 #include "lizard_gpu_ctx.h"
 #include "lizard_gpu_shim.h"
+#include "lizard_device_common.h"
 #include "unframes_kernels.h"
-
-#define LZ_HIP(call)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            snprintf(lzk_err(), LZK_ERR_BYTES, "%s failed: %s", #call, hipGetErrorString(e_));         \
-            return e_ == hipErrorOutOfMemory ? -LIZARDGPU_ERR_NOMEM : -LIZARDGPU_ERR_HIP;              \
-        }                                                                                              \
-    } while (0)
-
-#define LZU_E(code)       ((size_t)-(long)(LIZARDGPU_FRAME_ERR_##code))
-
-size_t lzgpu_frame_block_size(unsigned blockSizeID);         /* lizard_frame_host.c */
 
 enum { U_OPEN = 0, U_DECIDED = 1, U_DELEGATE = 2 };           /* a frame's state on the host */
 
@@ -163,16 +151,6 @@ static int u_fill_pass(UJob* j, int anyHash)
     return 0;
 }
 
-static void u_quiesce(LzCtx* c)                                /* nothing of this call stays in flight; the error text survives */
-{
-    char keep[LZK_ERR_BYTES];
-    int i;
-    memcpy(keep, lzk_err(), sizeof keep);
-    for (i = 0; i < LZ_STAGES; i++) if (c->stage[i].stream) (void)hipStreamSynchronize(c->stage[i].stream);
-    (void)hipGetLastError();
-    memcpy(lzk_err(), keep, sizeof keep);
-}
-
 static void u_first_refusal(size_t nFrames, const size_t* results)      /* the error text of a call that did its work: the first frame that was refused */
 {
     size_t i;
@@ -248,13 +226,13 @@ int LizardGPU_decompressFrames_device(size_t nFrames, void* const* d_dsts, const
     j.nFrames = nFrames; j.dsts = d_dsts; j.caps = dstCapacities; j.srcs = d_srcs; j.sizes = srcSizes; j.flags = flags;
     if (!(j.state = (unsigned char*)calloc(nFrames, 1))) {
         snprintf(lzk_err(), LZK_ERR_BYTES, "out of host memory");
-        for (i = 0; i < nFrames; i++) { results[i] = LZU_E(GENERIC); if (srcConsumed) srcConsumed[i] = 0; }
+        for (i = 0; i < nFrames; i++) { results[i] = LZ_FRAME_E(GENERIC); if (srcConsumed) srcConsumed[i] = 0; }
         return -LIZARDGPU_ERR_NOMEM;
     }
     for (i = 0; i < nFrames; i++) {
         results[i] = 0;
         if (srcConsumed) srcConsumed[i] = 0;
-        if ((!d_dsts[i] && dstCapacities[i]) || (!d_srcs[i] && srcSizes[i])) { results[i] = LZU_E(GENERIC); j.state[i] = U_DECIDED; }
+        if ((!d_dsts[i] && dstCapacities[i]) || (!d_srcs[i] && srcSizes[i])) { results[i] = LZ_FRAME_E(GENERIC); j.state[i] = U_DECIDED; }
         else open++;
     }
     rc = 0;
@@ -264,16 +242,16 @@ int LizardGPU_decompressFrames_device(size_t nFrames, void* const* d_dsts, const
         if (!rc) {
             j.c = g.c;
             rc = u_batch(&j, results, srcConsumed, (hipStream_t)stream);
-            u_quiesce(g.c);
+            lz_quiesce(g.c);
             lzk_guard_release(&g);                             /* (the single-frame entry takes it itself) */
         }
     }
     if (rc) {
         char keep[LZK_ERR_BYTES];
-        memcpy(keep, lzk_err(), sizeof keep);
-        for (i = 0; i < nFrames; i++) if (j.state[i] != U_DECIDED) { results[i] = LZU_E(GENERIC); if (srcConsumed) srcConsumed[i] = 0; }
+        lz_err_save(keep);
+        for (i = 0; i < nFrames; i++) if (j.state[i] != U_DECIDED) { results[i] = LZ_FRAME_E(GENERIC); if (srcConsumed) srcConsumed[i] = 0; }
         free(j.state);
-        memcpy(lzk_err(), keep, sizeof keep);
+        lz_err_restore(keep);
         return rc;
     }
     for (i = 0; i < nFrames; i++) {
@@ -285,18 +263,6 @@ int LizardGPU_decompressFrames_device(size_t nFrames, void* const* d_dsts, const
     free(j.state);
     u_first_refusal(nFrames, results);
     return 0;
-}
-
-static void u_info(LizardGPU_frameInfo_t* info, const LzWalkResult* r)
-{
-    memset(info, 0, sizeof *info);
-    info->frameType = (LizardF_frameType_t)r->frameType;
-    info->contentSize = r->contentSize;
-    if (!r->frameType) {
-        info->blockSizeID = (LizardF_blockSizeID_t)r->blockSizeID;
-        info->blockMode = (LizardF_blockMode_t)r->blockMode;
-        info->contentChecksumFlag = (LizardF_contentChecksum_t)r->checksumFlag;
-    }
 }
 
 int LizardGPU_framesInfo_device(size_t nFrames, const void* const* d_srcs, const size_t* srcSizes, LizardGPU_frameInfo_t* infos,
@@ -333,12 +299,12 @@ int LizardGPU_framesInfo_device(size_t nFrames, const void* const* d_srcs, const
             for (i = 0; i < nFrames && !rc; i++) {
                 const LzWalkResult* w = &j.h_walk[i];
                 if (j.state[i] != U_OPEN) continue;
-                if (infos && w->infoValid) u_info(&infos[i], w);
+                if (infos && w->infoValid) lz_walk_info(&infos[i], w);
                 if (w->status) { if (codes) codes[i] = -(int)w->status; continue; }
                 if (nRecords) nRecords[i] = (size_t)w->nRecords;
                 if (frameBytes) frameBytes[i] = (size_t)w->frameBytes;
             }
-            u_quiesce(g.c);
+            lz_quiesce(g.c);
             lzk_guard_release(&g);
         }
     }
@@ -349,11 +315,5 @@ int LizardGPU_framesInfo_device(size_t nFrames, const void* const* d_srcs, const
 
 int LizardGPU_framesDecodeDeviceStats(unsigned long long out[4])
 {
-    LzCtx* c = lzk_ctx_peek();
-    if (!out) return -LIZARDGPU_ERR_ARG;
-    if (!c) return -LIZARDGPU_ERR_NO_DEVICE;
-    pthread_mutex_lock(&c->mu);
-    memcpy(out, c->devFramesDecodeStats, 4 * sizeof out[0]);
-    pthread_mutex_unlock(&c->mu);
-    return 0;
+    return lz_stats_read(out, offsetof(LzCtx, devFramesDecodeStats));
 }

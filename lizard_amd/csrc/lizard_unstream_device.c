@@ -35,18 +35,9 @@
 #include "../../include/lizard_amd.h"
 #include "lizard_gpu_ctx.h"
 #include "lizard_gpu_shim.h"
+#include "lizard_device_common.h"
 #include "unstream_kernels.h"
 
-#define LZS_HIP(call)                                                                                  \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            snprintf(lzk_err(), LZK_ERR_BYTES, "%s failed: %s", #call, hipGetErrorString(e_));         \
-            return e_ == hipErrorOutOfMemory ? -LIZARDGPU_ERR_NOMEM : -LIZARDGPU_ERR_HIP;              \
-        }                                                                                              \
-    } while (0)
-
-#define LZS_E(code)       ((size_t)-(long)(LIZARDGPU_FRAME_ERR_##code))
 #define LZS_WALK_FRAMES   4096
 #define LZS_CTL_BYTES     64                                  /* the control record's share of the device / pinned layout */
 #define LZS_UNKNOWN       (~(uint64_t)0)
@@ -66,16 +57,6 @@ typedef struct {
     size_t end; unsigned why;                                 /* where the last segment stopped and why (LZS_*; 0: nothing walked yet) */
     unsigned long long segments;
 } STab;
-
-static void s_quiesce(LzCtx* c)                                /* nothing of this call stays in flight; the error text survives */
-{
-    char keep[LZK_ERR_BYTES];
-    int i;
-    memcpy(keep, lzk_err(), sizeof keep);
-    for (i = 0; i < LZ_STAGES; i++) if (c->stage[i].stream) (void)hipStreamSynchronize(c->stage[i].stream);
-    (void)hipGetLastError();
-    memcpy(lzk_err(), keep, sizeof keep);
-}
 
 /* One segment from `pos`, under the context guard: the control record goes up, the walk runs behind what the caller's stream holds, the
  * control record and the table come down: one wait.  The entries are appended to t. */
@@ -108,14 +89,14 @@ static int s_segment_locked(LzCtx* c, STab* t, size_t pos, hipStream_t stream)
     memset(h_ctl, 0, LZS_CTL_BYTES);
     h_ctl->pos = (uint64_t)pos;
     c->hostKernelMs = -1.0f;
-    LZS_HIP(hipEventRecord(s[0].up, stream));
-    LZS_HIP(hipStreamWaitEvent(S, s[0].up, 0));
-    LZS_HIP(hipMemcpyAsync(c->dfTab, h_ctl, LZS_CTL_BYTES, hipMemcpyHostToDevice, S));
+    LZ_HIP(hipEventRecord(s[0].up, stream));
+    LZ_HIP(hipStreamWaitEvent(S, s[0].up, 0));
+    LZ_HIP(hipMemcpyAsync(c->dfTab, h_ctl, LZS_CTL_BYTES, hipMemcpyHostToDevice, S));
     if ((rc = lzk_unstream_walk_launch(t->src, t->srcSize, (LzStreamCtl*)c->dfTab, (LzWalkResult*)(c->dfTab + LZS_CTL_BYTES),
                                        (uint64_t*)(c->dfTab + LZS_CTL_BYTES + T * sizeof(LzWalkResult)), (uint32_t)T, S))) return rc;
-    LZS_HIP(hipMemcpyAsync(h_down, c->dfTab, bytes, hipMemcpyDeviceToHost, S));
-    LZS_HIP(hipEventRecord(s[0].meta, S));
-    LZS_HIP(hipEventSynchronize(s[0].meta));
+    LZ_HIP(hipMemcpyAsync(h_down, c->dfTab, bytes, hipMemcpyDeviceToHost, S));
+    LZ_HIP(hipEventRecord(s[0].meta, S));
+    LZ_HIP(hipEventSynchronize(s[0].meta));
     h_ctl = (LzStreamCtl*)h_down;
     got = (size_t)h_ctl->nFrames;
     if (got > T || h_ctl->why < LZS_END || h_ctl->why > LZS_REFUSED || h_ctl->pos > (uint64_t)t->srcSize || (!got && h_ctl->why != LZS_END)) {
@@ -136,7 +117,7 @@ static int s_segment(STab* t, size_t pos, hipStream_t stream)
     lzk_guard_acquire(&g);
     if (g.rc) return g.rc;
     rc = s_segment_locked(g.c, t, pos, stream);
-    if (rc) s_quiesce(g.c);                                    /* (a segment that succeeded ended in its one wait: nothing is in flight) */
+    if (rc) lz_quiesce(g.c);                                   /* (a segment that succeeded ended in its one wait: nothing is in flight) */
     lzk_guard_release(&g);
     return rc;
 }
@@ -159,13 +140,13 @@ static void s_stats_add(const unsigned long long add[4])       /* the error text
     char keep[LZK_ERR_BYTES];
     LzCtx* c;
     int i;
-    memcpy(keep, lzk_err(), sizeof keep);
+    lz_err_save(keep);
     if ((c = lzk_ctx_peek())) {
         pthread_mutex_lock(&c->mu);
         for (i = 0; i < 4; i++) c->devStreamDecodeStats[i] += add[i];
         pthread_mutex_unlock(&c->mu);
     }
-    memcpy(lzk_err(), keep, sizeof keep);
+    lz_err_restore(keep);
 }
 
 static void s_name_failure(int rc)                             /* a failure of the machinery never leaves without a text */
@@ -202,7 +183,7 @@ size_t LizardGPU_decompressStream_device(void* d_dst, size_t dstCapacity, const 
     if (srcConsumedPtr) *srcConsumedPtr = 0;
     if (nFramesPtr) *nFramesPtr = 0;
     if (decodedPtr) *decodedPtr = 0;
-    if ((!d_dst && dstCapacity) || !d_src) { snprintf(lzk_err(), LZK_ERR_BYTES, "bad argument (null pointer)"); return LZS_E(GENERIC); }
+    if ((!d_dst && dstCapacity) || !d_src) { snprintf(lzk_err(), LZK_ERR_BYTES, "bad argument (null pointer)"); return LZ_FRAME_E(GENERIC); }
     memset(&t, 0, sizeof t);
     memset(&b, 0, sizeof b);
     t.src = (const uint8_t*)d_src; t.srcSize = srcSize;
@@ -272,22 +253,10 @@ size_t LizardGPU_decompressStream_device(void* d_dst, size_t dstCapacity, const 
     if (srcConsumedPtr) *srcConsumedPtr = pos;
     if (nFramesPtr) *nFramesPtr = frames;
     if (decodedPtr) *decodedPtr = out;
-    if (rc) { s_name_failure(rc); return LZS_E(GENERIC); }
+    if (rc) { s_name_failure(rc); return LZ_FRAME_E(GENERIC); }
     if (stop) return answer;
     lzk_err()[0] = 0;
     return out;
-}
-
-static void s_info(LizardGPU_frameInfo_t* info, const LzWalkResult* r)
-{
-    memset(info, 0, sizeof *info);
-    info->frameType = (LizardF_frameType_t)r->frameType;
-    info->contentSize = r->contentSize;
-    if (!r->frameType) {
-        info->blockSizeID = (LizardF_blockSizeID_t)r->blockSizeID;
-        info->blockMode = (LizardF_blockMode_t)r->blockMode;
-        info->contentChecksumFlag = (LizardF_contentChecksum_t)r->checksumFlag;
-    }
 }
 
 int LizardGPU_streamIndex_device(const void* d_src, size_t srcSize, uint64_t* frameOffsets, uint64_t* frameBytes, LizardGPU_frameInfo_t* infos,
@@ -309,7 +278,7 @@ int LizardGPU_streamIndex_device(const void* d_src, size_t srcSize, uint64_t* fr
         if ((rc = s_segment(&t, pos, (hipStream_t)stream))) break;
         for (i = 0; i < t.n; i++) {
             const LzWalkResult* w = &t.w[i];
-            if (count < maxFrames && infos && w->infoValid) s_info(&infos[count], w);
+            if (count < maxFrames && infos && w->infoValid) lz_walk_info(&infos[count], w);
             if (s_refused(&t, i)) { code = -(int)(w->status ? w->status : LIZARDGPU_FRAME_ERR_GENERIC); break; }
             if (count < maxFrames) {
                 if (frameOffsets) frameOffsets[count] = t.off[i];
@@ -332,11 +301,5 @@ int LizardGPU_streamIndex_device(const void* d_src, size_t srcSize, uint64_t* fr
 
 int LizardGPU_streamDecodeDeviceStats(unsigned long long out[4])
 {
-    LzCtx* c = lzk_ctx_peek();
-    if (!out) return -LIZARDGPU_ERR_ARG;
-    if (!c) return -LIZARDGPU_ERR_NO_DEVICE;
-    pthread_mutex_lock(&c->mu);
-    memcpy(out, c->devStreamDecodeStats, 4 * sizeof out[0]);
-    pthread_mutex_unlock(&c->mu);
-    return 0;
+    return lz_stats_read(out, offsetof(LzCtx, devStreamDecodeStats));
 }

@@ -306,11 +306,33 @@ struct LzUnBatch {
     u8* scratch; u32* counter;
 };
 #define LZ_WAVES_DEC 16
+
+// The persistent grid of the decode kernels: a wave claims index after index below n from the launch's counter and calls
+// body(b, stage, ws) with its scratch slot and its LDS workspace; all lanes call, and lane 0 of the body stores what the item came
+// to.  What item b is and where it goes is the kernel's own business.  lz_unframe_inplace_kernel (unframe_kernels.h) and
+// lz_unframes_kernel (unframes_kernels.h) are one call of it.  lz_decompress_kernel below and lz_unframe_kernel state the same loop
+// themselves: both clamp a launch-wide capacity, and through the closure the compiler hoists that clamp out of the loop in a later
+// pass and schedules the prologue differently (same instructions, another order and register assignment).
+template <class Body>
+LZ_DEV void lz_decode_grid(u32* counter, u32 n, u8* scratch, Body body)
+{
+    __shared__ u32 ws[LZ_WAVES_DEC][LZD_WS_WORDS];
+    const u32 wave = lz_uniform(threadIdx.x >> 6);
+    u8* stage = scratch + ((u64)blockIdx.x * LZ_MAX_WAVES + wave) * LZ_SCRATCH_BYTES;       // 4 x LZD_STAGE_BYTES fit a scratch slot
+    for (;;) {
+        lz_converge();
+        const u32 b = lz_claim_index(counter);
+        if (b >= n) break;
+        body(b, stage, ws[wave]);
+        lz_converge();
+    }
+}
+
 __global__ __launch_bounds__(64 * LZ_WAVES_DEC) void lz_decompress_kernel(LzUnBatch a)
 {
     __shared__ u32 ws[LZ_WAVES_DEC][LZD_WS_WORDS];
     const u32 wave = lz_uniform(threadIdx.x >> 6);
-    u8* stage = a.scratch + ((u64)blockIdx.x * LZ_MAX_WAVES + wave) * LZ_SCRATCH_BYTES;     // 4 x LZD_STAGE_BYTES fit a scratch slot
+    u8* stage = a.scratch + ((u64)blockIdx.x * LZ_MAX_WAVES + wave) * LZ_SCRATCH_BYTES;
     for (;;) {
         lz_converge();
         const u32 b = lz_claim_index(a.counter);

@@ -37,7 +37,8 @@ struct LzUnframeBatch {
     u8* scratch; u32* counter;
 };
 
-// Persistent grid, one wave per record, LDS workspace and scratch slot as lz_decompress_kernel (lz_kernels.h) uses them.
+// Persistent grid, one wave per record, LDS workspace and scratch slot as lz_decompress_kernel (lz_kernels.h) uses them; like that
+// kernel it keeps the loop of lz_decode_grid in its own words (lz_kernels.h says why).
 __global__ __launch_bounds__(64 * LZ_WAVES_DEC) void lz_unframe_kernel(LzUnframeBatch a)
 {
     __shared__ u32 ws[LZ_WAVES_DEC][LZD_WS_WORDS];
@@ -66,22 +67,15 @@ struct LzUnframeInPlaceBatch {
 
 __global__ __launch_bounds__(64 * LZ_WAVES_DEC) void lz_unframe_inplace_kernel(LzUnframeInPlaceBatch a)
 {
-    __shared__ u32 ws[LZ_WAVES_DEC][LZD_WS_WORDS];
-    const u32 wave = lz_uniform(threadIdx.x >> 6);
-    u8* stage = a.scratch + ((u64)blockIdx.x * LZ_MAX_WAVES + wave) * LZ_SCRATCH_BYTES;
-    for (;;) {
-        lz_converge();
-        const u32 b = lz_claim_index(a.counter);
-        if (b >= a.nRecords) break;
+    lz_decode_grid(a.counter, a.nRecords, a.scratch, [&](u32 b, u8* stage, u32* ws) {
         const u64 at = (u64)b * a.slotBytes;
         u32 r = LZD_ERR;
         if (at < a.dstRoom) {
             u64 room = a.dstRoom - at;
             if (room > a.slotBytes) room = a.slotBytes;
-            r = lz_unframe_record(a.src + a.payloadOffsets[b], a.words[b], a.dst + at, room > 0x7FFFFFFFull ? 0x7FFFFFFFu : (u32)room, stage, ws[wave]);
+            r = lz_unframe_record(a.src + a.payloadOffsets[b], a.words[b], a.dst + at, room > 0x7FFFFFFFull ? 0x7FFFFFFFu : (u32)room, stage, ws);
         }
         if (lz_lane() == 0) { a.outSizes[b] = r; a.packSizes[b] = r >= LZD_NEED_HISTORY ? 0u : r; }
-        lz_converge();
-    }
+    });
 }
 #endif

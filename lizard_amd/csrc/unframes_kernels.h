@@ -108,27 +108,20 @@ struct LzUnframesBatch {
     u8* scratch; u32* counter;
 };
 
-// Persistent grid, one wave per record, LDS workspace and scratch slot as lz_unframe_inplace_kernel (unframe_kernels.h) uses them.
+// One wave per record on the persistent grid of the decode kernels (lz_decode_grid, lz_kernels.h), like lz_unframe_inplace_kernel.
 __global__ __launch_bounds__(64 * LZ_WAVES_DEC) void lz_unframes_kernel(LzUnframesBatch a)
 {
-    __shared__ u32 ws[LZ_WAVES_DEC][LZD_WS_WORDS];
-    const u32 wave = lz_uniform(threadIdx.x >> 6);
-    u8* stage = a.scratch + ((u64)blockIdx.x * LZ_MAX_WAVES + wave) * LZ_SCRATCH_BYTES;
-    for (;;) {
-        lz_converge();
-        const u32 b = lz_claim_index(a.counter);
-        if (b >= a.nRecords) break;
+    lz_decode_grid(a.counter, a.nRecords, a.scratch, [&](u32 b, u8* stage, u32* ws) {
         const LzUnframesEntry* const e = a.frames + a.recFrame[b];
         const u64 slot = e->maxBlock, cap = e->cap, at = ((u64)b - e->first) * slot;
         u32 r = LZD_ERR;
         if (at < cap) {
             const u64 room = cap - at < slot ? cap - at : slot;                  // (a block size is 256 MiB at most)
             r = lz_unframe_record(reinterpret_cast<const u8*>(e->src) + a.offs[b], a.words[b], reinterpret_cast<u8*>(e->dst) + at, (u32)room,
-                                  stage, ws[wave]);
+                                  stage, ws);
         }
         if (lz_lane() == 0) a.out[b] = r;
-        lz_converge();
-    }
+    });
 }
 #endif
 
