@@ -437,13 +437,70 @@ struct LzTab {
 // (both arrays dword-aligned, with room for the trash slot's dword: the exchanges are dword atomics)
 #define LZ_TAB_BYTES(HASHLOG) ((3u << (HASHLOG)) + 8u)
 template <int HASHLOG> LZ_DEV LzTab lz_tab_bind(void* mem) { LzTab t; t.lo = (LZ_LDS u16*)mem; t.hi = (LZ_LDS u8*)mem + (2u << HASHLOG) + 4u; return t; }
-// Re-stamp every slot that is dead at position Ps (age >= 65536); with `fresh`: all empty.
+// Re-stamp every slot that is dead at position Ps (age >= 65536); with `fresh`: all empty.  One slot per lane and trip: 2^HASHLOG / 64
+// trips of two LDS loads, a wait, and two stores inside a per-slot exec region.
 template <int HASHLOG>
-LZ_DEV void lz_tab_sweep(const LzTab& t, u32 Ps, bool fresh)
+LZ_DEV void lz_tab_sweep_narrow(const LzTab& t, u32 Ps, bool fresh)
 {
     const u32 dead = (Ps + 65536u) & 0x1FFFFu;
     for (u32 i = lz_lane(); i < (1u << HASHLOG); i += 64u)
         if (fresh || t.age(Ps, t.get(i)) >= 65536u) t.set(i, dead);
+}
+// LZ_WIDE_SWEEP: the same sweep four neighbouring slots per lane and step (profiles/producer_sweep_ab.txt).  A step reads the four u16
+// of `lo` as two dwords and the four u8 of `hi` as one, picks `dead` per slot and writes all three dwords back whether anything
+// changed or not: the wave owns its table and the LDS operations of one wave execute in issue order, so the unconditional write of
+// a selected value is the conditional store.  2^HASHLOG / 256 steps, straight-line, the loads of four steps issued before the first
+// is used; no exec region, no branch.  Both arrays are only dword-aligned (a workgroup's tables are LZ_TAB_BYTES + 4 apart, `hi`
+// starts 4 bytes behind a multiple of 8), hence dword pairs and not 8-byte words.  The trash slot (index 2^HASHLOG) is not swept.
+// A slot is dead iff bit 16 of Ps - position is set: age = (Ps - ent) & 0x1FFFF, and the check bits above bit 16 do not reach it.
+#ifndef LZ_WIDE_SWEEP
+#define LZ_WIDE_SWEEP 1
+#endif
+typedef u32 __attribute__((may_alias)) lz_tab_word;             // a dword of `lo` (two slots) or of `hi` (four)
+template <int HASHLOG>
+LZ_DEV void lz_tab_sweep_wide(const LzTab& t, u32 Ps)
+{
+    static_assert((1u << HASHLOG) % 1024u == 0u, "four steps of 256 slots at a time");
+    constexpr u32 kSteps = (1u << HASHLOG) / 256u, kBatch = 4u;
+    const u32 dead = (Ps + 65536u) & 0x1FFFFu;
+    const u32 dlo = (dead & 0xFFFFu) * 0x10001u, dhi = (dead >> 16) * 0x01010101u;
+    LZ_LDS lz_tab_word* const pl = (LZ_LDS lz_tab_word*)t.lo + 2u * lz_lane();
+    LZ_LDS lz_tab_word* const ph = (LZ_LDS lz_tab_word*)t.hi + lz_lane();
+#pragma unroll
+    for (u32 s0 = 0; s0 < kSteps; s0 += kBatch) {
+        u32 la[kBatch], lb[kBatch], h[kBatch];
+#pragma unroll
+        for (u32 k = 0; k < kBatch; k++) { la[k] = pl[(s0 + k) * 128u]; lb[k] = pl[(s0 + k) * 128u + 1u]; h[k] = ph[(s0 + k) * 64u]; }
+#pragma unroll
+        for (u32 k = 0; k < kBatch; k++) {
+            // all-ones where the slot is dead: bit 16 of Ps - (lo | (hi & 1) << 16), spread over the word
+            const u32 m0 = 0u - (((Ps - ((la[k] & 0xFFFFu) | ((h[k] & 0x00000001u) << 16))) >> 16) & 1u);
+            const u32 m1 = 0u - (((Ps - ((la[k] >> 16)     | ((h[k] & 0x00000100u) << 8))) >> 16) & 1u);
+            const u32 m2 = 0u - (((Ps - ((lb[k] & 0xFFFFu) | ((h[k] & 0x00010000u))))      >> 16) & 1u);
+            const u32 m3 = 0u - (((Ps - ((lb[k] >> 16)     | ((h[k] & 0x01000000u) >> 8))) >> 16) & 1u);
+            const u32 ma = (m0 & 0x0000FFFFu) | (m1 & 0xFFFF0000u), mb = (m2 & 0x0000FFFFu) | (m3 & 0xFFFF0000u);
+            const u32 mh = (m0 & 0x000000FFu) | (m1 & 0x0000FF00u) | (m2 & 0x00FF0000u) | (m3 & 0xFF000000u);
+            pl[(s0 + k) * 128u] = (la[k] & ~ma) | (dlo & ma); pl[(s0 + k) * 128u + 1u] = (lb[k] & ~mb) | (dlo & mb);
+            ph[(s0 + k) * 64u] = (h[k] & ~mh) | (dhi & mh);
+        }
+    }
+}
+// The fresh table is a constant fill: `dead` at Ps = 0 is 0x10000, so `lo` is all zero and `hi` all 0x01.
+template <int HASHLOG>
+LZ_DEV void lz_tab_fresh_wide(const LzTab& t)
+{
+    static_assert((1u << HASHLOG) % 256u == 0u, "256 slots a step");
+    constexpr u32 kSteps = (1u << HASHLOG) / 256u;
+    LZ_LDS lz_tab_word* const pl = (LZ_LDS lz_tab_word*)t.lo + 2u * lz_lane();
+    LZ_LDS lz_tab_word* const ph = (LZ_LDS lz_tab_word*)t.hi + lz_lane();
+#pragma unroll
+    for (u32 s = 0; s < kSteps; s++) { pl[s * 128u] = 0u; pl[s * 128u + 1u] = 0u; ph[s * 64u] = 0x01010101u; }
+}
+template <int HASHLOG>
+LZ_DEV void lz_tab_sweep(const LzTab& t, u32 Ps, bool fresh)
+{
+    if constexpr (LZ_WIDE_SWEEP != 0 && (1u << HASHLOG) % 1024u == 0u) { if (fresh) lz_tab_fresh_wide<HASHLOG>(t); else lz_tab_sweep_wide<HASHLOG>(t, Ps); }
+    else lz_tab_sweep_narrow<HASHLOG>(t, Ps, fresh);
 }
 template <int HASHLOG> LZ_DEV void lz_tab_fresh(const LzTab& t) { lz_tab_sweep<HASHLOG>(t, 0, true); }
 

@@ -13,7 +13,12 @@
 // the word at its head.  A consumer hands a buffer back through a bit in the producer's free mask.  Everything a job needs
 // beyond the sequence list travels in the header; the waves of a workgroup share nothing else, and a producer only ever waits
 // for a free buffer, a consumer only for a job: no cycle, no deadlock.  Memory order: the header and the list are global-memory
-// stores; release / acquire fences at agent scope around the LDS word that publishes them.
+// stores; release / acquire fences at WORKGROUP scope around the LDS word that publishes them (lz_publish_release / lz_publish_acquire,
+// lz_wave.h: producer and consumer are waves of one workgroup on one CU and share its vector L1).  What crosses between waves in
+// global memory: the job header (plain stores; read with lz_ld_shared_u32), the sequence list (global_store_dwordx2; plain loads),
+// and in the reverse direction the buffer itself — the consumer's lz_wave_sync() behind its last read of the list, then its bit in
+// bufFree, then the producer's overwrite.  opSlot is the consumer's own word, sizes[] is read after the kernel, and the device-wide
+// block counter is an atomic outside the hand-over.
 //
 // Test infrastructure runs this file on the CPU with several emulated waves on OS threads (tests/emul, emul_compress_split).
 #pragma once

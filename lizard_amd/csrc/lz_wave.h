@@ -145,17 +145,47 @@ LZ_DEV u32 lz_lds_poll_u(const u32* p) { return lz_uniform(lz_lds_poll(p)); }
 //   lz_lds_claim       take the next ticket of an LDS counter: one atomic per wave, result wave-uniform (branch-free like lz_claim_index)
 //   lz_lds_store       store of a word other waves poll (lz_lds_poll)
 //   lz_publish_release / lz_publish_acquire   around such a word when it announces GLOBAL-memory data written by this wave / to be read
-//                      by this wave: all earlier stores of every lane have completed (agent scope) before the word is stored; the
-//                      vector L1 is invalidated after the word was seen, so reused buffers are re-read from L2
+//                      by this wave: the wave that sees the word sees all earlier stores of every lane of the wave that stored it, and
+//                      none of its later loads is served from before the word was seen.  The two waves are always waves of ONE workgroup, and the library is
+//                      built without threadgroup-split mode, so they run on one CU and share its vector L1: workgroup scope is the
+//                      contract (the one __syncthreads() gives global data).  For gfx950 the compiler makes a workgroup-scope release
+//                      s_waitcnt lgkmcnt(0) and an acquire no instruction: the vector memory instructions of all waves of a CU reach
+//                      its L1 in the order they were issued, so a load issued behind the word meets the stores issued in front of
+//                      it without a vmcnt wait (LLVM AMDGPUUsage, memory model of gfx90a / gfx942: outside tgsplit mode the
+//                      vmcnt(0) of a workgroup-scope release is omitted).  At agent scope (LZ_HANDOVER_WG=0) the release is buffer_wbl2 sc1 — a write-back request to
+//                      the L2 — and s_waitcnt vmcnt(0) lgkmcnt(0), and the acquire is buffer_inv sc1, which drops the CU's whole
+//                      vector L1 and the L2's non-local lines, for every wave that shares them, once per job.
+//                      What crosses between waves in global memory, and what each piece rests on:
+//                        job header      written with plain stores before the release; read with lz_ld_shared_u32 (a relaxed atomic
+//                                        load: never from the scalar cache, never from a stale L1 line)
+//                        sequence list   global_store_dwordx2 before the release; plain vector loads behind the acquire.  Vector stores
+//                                        go through the write-through L1 that both waves share, in issue order; that one L1 serves
+//                                        the consumer's loads, so a line it kept from an earlier use of the buffer cannot be older
+//                                        than the producer's store (same source: wavefronts of a work-group share the CU's L1 outside
+//                                        tgsplit mode, no action is needed between them)
+//                        buffer reuse    the consumer's last reads of the list are issued, and its output computed from them, in front
+//                                        of its lz_wave_sync() (workgroup scope) and the bufFree bit behind it; the producer's stores
+//                                        into the buffer are issued behind the bit, so behind those loads in the L1 both use
+//                        opSlot, sizes[] opSlot is the consumer's own word (lz_st_shared_u32 / lz_ld_shared_u32); sizes[] is read
+//                                        after the kernel
+//                        block counter   a device-wide atomic, not part of the hand-over
 //   lz_ld_shared_u32 / lz_st_shared_u32        a global-memory word handed between waves (never served from the scalar cache)
+#ifndef LZ_HANDOVER_WG
+#define LZ_HANDOVER_WG 1
+#endif
+#if LZ_HANDOVER_WG
+#define LZ_HANDOVER_SCOPE "workgroup"
+#else
+#define LZ_HANDOVER_SCOPE "agent"
+#endif
 LZ_DEV u32 lz_lds_claim(u32* counter)
 {
     const u32 old = atomicAdd(counter, lz_lane() == 0 ? 1u : 0u);
     return lz_readlane(old, 0);
 }
 LZ_DEV void lz_lds_store(u32* p, u32 v) { __atomic_store_n(p, v, __ATOMIC_RELAXED); }
-LZ_DEV void lz_publish_release() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); __builtin_amdgcn_wave_barrier(); }
-LZ_DEV void lz_publish_acquire() { __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); }
+LZ_DEV void lz_publish_release() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, LZ_HANDOVER_SCOPE); __builtin_amdgcn_wave_barrier(); }
+LZ_DEV void lz_publish_acquire() { __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, LZ_HANDOVER_SCOPE); }
 LZ_DEV u32 lz_ld_shared_u32(const u32* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
 LZ_DEV void lz_st_shared_u32(u32* p, u32 v) { __atomic_store_n(p, v, __ATOMIC_RELAXED); }
 // Masked bit-field store into an LDS dword, atomic per lane: *p = (*p & ~mask) | val  (ds_mskor_b32).  Lanes of one
