@@ -16,7 +16,8 @@
  *   Part 3b  whole-frame decompression on the GPU (LizardGPU_decompressFrame, LizardGPU_decompressFrame_device,
  *            LizardGPU_decompressFrames_device, LizardGPU_decompressStream_device ...)
  *   Part 3c  tensor streams: element bytes split into planes before compressing (LizardGPU_splitPlanes_device,
- *            LizardGPU_joinPlanes_device) and the tensor header, a skippable frame (LizardGPU_tensorHeaderWrite / Read)
+ *            LizardGPU_joinPlanes_device) or, opt-in, element bits (LizardGPU_splitBitPlanes_device, LizardGPU_joinBitPlanes_device),
+ *            and the tensor header, a skippable frame (LizardGPU_tensorHeaderWrite / Read, with a filter: Write2 / Read2)
  *
  * Plain C, plain pointers and sizes; no HIP or torch types in any signature (a HIP stream is passed
  * as an opaque void*).
@@ -655,8 +656,9 @@ int LizardGPU_streamDecodeDeviceStats(unsigned long long out[4]);
  * The bytes of a buffer of `size` bytes with element size E in {1, 2, 4, 8}, n = size / E elements, regrouped by significance
  * (what Blosc calls "shuffle"):  split writes dst[p * n + i] = src[i * E + p] for p < E, i < n and copies the size - n * E tail
  * bytes to dst + n * E; join is the exact inverse; E = 1 is a copy.  Interleaved, the exponent byte of a float is hidden from a
- * byte-oriented LZ parser and from huff0; in a plane of its own it has 2.7 bits of entropy for bf16 and fp32 weights.  fp16 gains
- * nothing at these levels: its top byte holds 5.5 bits and the Huffman stage stores it raw.
+ * byte-oriented LZ parser and from huff0; in a plane of its own it has 2.7 bits of entropy for bf16 and fp32 weights.  With BYTE
+ * planes fp16 gains nothing at these levels: its top byte holds 5.5 bits and the Huffman stage stores it raw (the bit planes
+ * below are the filter for fp16).
  *
  * A batch of buffers in ONE launch each way (planes_kernels.h).  d_dsts, d_srcs, sizes, elemSizes: HOST arrays of nBuffers entries;
  * the pointers are device pointers on the selected device and may have any alignment (the kernels are fastest when both are
@@ -699,6 +701,57 @@ typedef struct { uint32_t elemSize; uint32_t ndim; uint64_t nbytes; uint64_t sha
 #define LIZARDGPU_TENSOR_MAGIC 0x184D2A54u
 size_t LizardGPU_tensorHeaderWrite(void* dst, size_t dstCapacity, const LizardGPU_tensorDesc_t* desc); /* bytes, or 0 */
 int    LizardGPU_tensorHeaderRead(const void* src, size_t srcSize, LizardGPU_tensorDesc_t* desc, size_t* headerBytes);
+
+/* Bit planes: the second filter (what Blosc and HDF5 call "bitshuffle"), OPT-IN.  The BITS of a buffer regrouped by weight: with
+ * n = size / E elements, n8 = n - n % 8 of them are transposed and a plane has P = n8 / 8 bytes.  Bit k (k < 8 E) of element i is
+ * (src[i * E + k / 8] >> (k % 8)) & 1, the bit of weight 2^k of the little-endian element.
+ *     split   dst[k * P + j] = sum over b < 8 of bit_k(element 8 j + b) << b     for k < 8 E, j < P
+ *             the bytes src[n8 * E .. size) — the last n % 8 elements and the bytes behind the last whole element — are copied
+ *             unchanged to dst[n8 * E .. size)
+ *     join    the exact inverse
+ * E = 1 is NOT a copy: it makes eight planes.  This is the bitshuffle library's bit order, applied to the whole buffer and not
+ * block-wise, as the byte planes are.  A nearly constant bit plane is a long run, which the LZ parser alone removes, with no
+ * Huffman stage, so the gain shows at level 10 already.  Stream / raw, reference library, 128 KiB blocks, randn(2^19) * 0.02
+ * (profiles/bitplanes_ratio.json):
+ *              level 10          level 21          level 30          level 41
+ *              bytes   bits      bytes   bits      bytes   bits      bytes   bits
+ *     fp16     1.0000  0.9375    1.0000  0.9375    1.0000  0.9375    1.0000  0.9375
+ *     bf16     0.8431  0.7645    0.8244  0.7531    0.7456  0.7504    0.7252  0.7531
+ *     fp32     0.9215  0.8825    0.9122  0.8766    0.8728  0.8753    0.8626  0.8766
+ * Choose it for fp16 at any level and for weight-like bf16 / fp32 at levels 10 .. 29, which then reach level 30's ratio with
+ * level 10's compressor and decoder.  It LOSES where the byte planes already feed huff0 well: bf16 randn * 1.0 (activation-like)
+ * 0.8359 bytes / 0.8721 bits at level 10 and 0.7429 / 0.8081 at level 30; int32 indices below 50 000 are 0.5002 either way;
+ * int64 arange(2^17) is 0.1107 bytes / 0.0043 bits at level 10.  A bf16 tensor of 8 KiB gains from neither at levels 10 and 30.
+ * The default stays the byte planes.
+ *
+ * LizardGPU_splitBitPlanes_device / LizardGPU_joinBitPlanes_device: the signature and the whole contract of
+ * LizardGPU_splitPlanes_device / LizardGPU_joinPlanes_device above (bitplanes_kernels.h; the host code is the same) — host arrays
+ * of device pointers of any alignment, SYNCHRONOUS and ordered after what `stream` holds, entries of size 0 skipped, NOT in place,
+ * nothing outside d_dsts[i][0 .. sizes[i]) written and nothing outside d_srcs[i][0 .. sizes[i]) read, -LIZARDGPU_ERR_ARG with
+ * NOTHING launched for a null array, an elemSizes[i] outside {1, 2, 4, 8}, a null pointer in an entry of non-zero size or a batch
+ * of 2^32 tiles or more, nBuffers == 0 returns 0.  LizardGPU_bitPlanesStats: their own counters — [0] buffers split, [1] buffers
+ * joined, [2] bytes moved, [3] launches —, so LizardGPU_planesStats keeps counting byte-plane calls only. */
+int LizardGPU_splitBitPlanes_device(size_t nBuffers, void* const* d_dsts, const void* const* d_srcs,
+                                    const size_t* sizes, const uint32_t* elemSizes, void* stream);
+int LizardGPU_joinBitPlanes_device (size_t nBuffers, void* const* d_dsts, const void* const* d_srcs,
+                                    const size_t* sizes, const uint32_t* elemSizes, void* stream);
+int LizardGPU_bitPlanesStats(unsigned long long out[4]);
+
+/* The tensor header with a filter.  LizardGPU_tensorHeaderWrite / Read above stay as they are, byte for byte, and go on refusing
+ * the tag "LZT2": a v1 reader cannot undo a v2 filter.  LizardGPU_tensorDesc2_t: the v1 fields, then the filter; `reserved` is
+ * written as zero and ignored on read.
+ * Write2: filter LIZARDGPU_FILTER_BYTE_PLANES writes exactly LizardGPU_tensorHeaderWrite's "LZT1" bytes — streams made with byte
+ * planes do not change and old readers read them; LIZARDGPU_FILTER_BIT_PLANES writes the same layout with the tag "LZT2", payload
+ * byte 6 = 1 (the filter) and byte 7 = 0; any other filter writes nothing and returns 0, like every refusal of Write.
+ * Read2: accepts "LZT1" (filter 0) and "LZT2" with payload byte 6 == 1 and byte 7 == 0; anything else under "LZT2" is
+ * -LIZARDGPU_FRAME_ERR_frameType_unknown, so every meaning has ONE encoding.  Everything else as Read: every field is judged as soon
+ * as the bytes in hand hold it, a prefix of a valid header is -LIZARDGPU_FRAME_ERR_frameHeader_incomplete, never unknown. */
+#define LIZARDGPU_FILTER_BYTE_PLANES 0
+#define LIZARDGPU_FILTER_BIT_PLANES  1
+typedef struct { uint32_t elemSize; uint32_t ndim; uint64_t nbytes; uint64_t shape[8]; char dtype[24];
+                 uint32_t filter; uint32_t reserved; } LizardGPU_tensorDesc2_t;
+size_t LizardGPU_tensorHeaderWrite2(void* dst, size_t dstCapacity, const LizardGPU_tensorDesc2_t* desc); /* bytes, or 0 */
+int    LizardGPU_tensorHeaderRead2(const void* src, size_t srcSize, LizardGPU_tensorDesc2_t* desc, size_t* headerBytes);
 
 #ifdef __cplusplus
 }

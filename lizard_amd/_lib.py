@@ -118,6 +118,12 @@ def lib():
     L.LizardGPU_joinPlanes_device.argtypes = [c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
     L.LizardGPU_joinPlanes_device.restype = c.c_int
     L.LizardGPU_planesStats.argtypes = [c.c_void_p]; L.LizardGPU_planesStats.restype = c.c_int
+    for name in ("LizardGPU_splitBitPlanes_device", "LizardGPU_joinBitPlanes_device"):
+        getattr(L, name).argtypes = [c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+        getattr(L, name).restype = c.c_int
+    L.LizardGPU_bitPlanesStats.argtypes = [c.c_void_p]; L.LizardGPU_bitPlanesStats.restype = c.c_int
+    L.LizardGPU_tensorHeaderWrite2.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p]; L.LizardGPU_tensorHeaderWrite2.restype = c.c_size_t
+    L.LizardGPU_tensorHeaderRead2.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]; L.LizardGPU_tensorHeaderRead2.restype = c.c_int
     L.LizardGPU_tensorHeaderWrite.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p]; L.LizardGPU_tensorHeaderWrite.restype = c.c_size_t
     L.LizardGPU_tensorHeaderRead.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]; L.LizardGPU_tensorHeaderRead.restype = c.c_int
     _lib = L

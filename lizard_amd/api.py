@@ -489,9 +489,14 @@ def decompress_stream_device(src, dst=None, size=None, verify_checksum=True):
 TENSOR_HEADER_MAX = 8 + 40 + 8 * 8          # bytes of the longest tensor header (ndim = 8)
 
 
+FILTER_BYTE_PLANES, FILTER_BIT_PLANES = 0, 1   # LIZARDGPU_FILTER_*: what a tensor header says its data frame's bytes were split with
+_PLANES_NAMES = {FILTER_BYTE_PLANES: "bytes", FILTER_BIT_PLANES: "bits"}
+
+
 class _TensorDesc(ctypes.Structure):
+    """LizardGPU_tensorDesc2_t: the v1 fields, then the filter."""
     _fields_ = [("elemSize", ctypes.c_uint32), ("ndim", ctypes.c_uint32), ("nbytes", ctypes.c_uint64), ("shape", ctypes.c_uint64 * 8),
-                ("dtype", ctypes.c_char * 24)]
+                ("dtype", ctypes.c_char * 24), ("filter", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 def _as_bytes(t):
@@ -509,7 +514,9 @@ def _plane_elem_size(t):
     return min(e, 8)
 
 
-def _planes_device(tensors, elem_sizes, join):
+def _planes_device(tensors, elem_sizes, join, filters=FILTER_BYTE_PLANES):
+    """`filters`: one LIZARDGPU_FILTER_* for all tensors or one per tensor; ONE launch per filter that occurs, all into one output
+    tensor."""
     import torch
     L = _lib.lib()
     tensors = list(tensors)
@@ -523,18 +530,24 @@ def _planes_device(tensors, elem_sizes, join):
         elem_sizes = [_plane_elem_size(t) for t in tensors]
     elem_sizes = [int(e) for e in elem_sizes]
     assert len(elem_sizes) == n
+    filters = [filters] * n if isinstance(filters, int) else [int(f) for f in filters]
+    assert len(filters) == n and all(f in _PLANES_NAMES for f in filters)
     sizes = [int(t.numel()) * t.element_size() for t in tensors]
     offsets, total = [], 0
     for s in sizes:
         offsets.append(total)
         total += (s + 255) & ~255
     out = torch.empty(max(total, 1), dtype=torch.uint8, device=device)
-    srcs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors])
-    dsts = (ctypes.c_void_p * n)(*[out.data_ptr() + o for o in offsets])
     L.LizardGPU_setDevice(device.index or 0)
     stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    fn, name = (L.LizardGPU_joinPlanes_device, "LizardGPU_joinPlanes_device") if join else (L.LizardGPU_splitPlanes_device, "LizardGPU_splitPlanes_device")
-    _lib.check(fn(n, dsts, srcs, (ctypes.c_size_t * n)(*sizes), (ctypes.c_uint32 * n)(*elem_sizes), stream), name)
+    for f in sorted(set(filters)):
+        name = "LizardGPU_%s%sPlanes_device" % ("join" if join else "split", "Bit" if f == FILTER_BIT_PLANES else "")
+        pick = [i for i in range(n) if filters[i] == f]
+        k = len(pick)
+        srcs = (ctypes.c_void_p * k)(*[tensors[i].data_ptr() for i in pick])
+        dsts = (ctypes.c_void_p * k)(*[out.data_ptr() + offsets[i] for i in pick])
+        _lib.check(getattr(L, name)(k, dsts, srcs, (ctypes.c_size_t * k)(*[sizes[i] for i in pick]),
+                                    (ctypes.c_uint32 * k)(*[elem_sizes[i] for i in pick]), stream), name)
     return [out[o:o + s] for o, s in zip(offsets, sizes)]
 
 
@@ -553,21 +566,48 @@ def join_planes_device(tensors, elem_sizes):
     return _planes_device(tensors, elem_sizes, True)
 
 
-def compress_tensors_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksum=False, split=True):
+def split_bit_planes_device(tensors, elem_sizes=None):
+    """The BITS of `tensors` regrouped by weight in ONE launch of LizardGPU_splitBitPlanes_device on torch's current stream — the twin
+    of split_planes_device, same arguments and result: for a tensor of n elements of E bytes, all bit 0 of every element, then all
+    bit 1, ... (include/lizard_amd.h Part 3c: dst[k * P + j] holds bit k of elements 8 j .. 8 j + 7, P = (n - n % 8) / 8; the last
+    n % 8 elements and the bytes behind the last whole element are copied).  An element size of 1 is NOT a copy: eight planes.
+    Returns uint8 views into ONE output tensor, at 256-byte-aligned offsets."""
+    return _planes_device(tensors, elem_sizes, False, FILTER_BIT_PLANES)
+
+
+def join_bit_planes_device(tensors, elem_sizes):
+    """The inverse of split_bit_planes_device for the same `elem_sizes`, in ONE launch of LizardGPU_joinBitPlanes_device: uint8 views
+    into one output tensor, at 256-byte-aligned offsets."""
+    return _planes_device(tensors, elem_sizes, True, FILTER_BIT_PLANES)
+
+
+def compress_tensors_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksum=False, split=True, planes="bytes"):
     """A .liz STREAM for `tensors`, contiguous CUDA tensors of any dtype and shape on one device (zero-element ones and scalars
     allowed), as ONE uint8 CUDA tensor: per tensor a tensor header — a skippable frame with the dtype's name, the shape and the
     element size of the split (LizardGPU_tensorHeaderWrite) — and one frame with content size over the tensor's bytes SPLIT INTO
     PLANES.  Every decoder of the format reads the stream (the headers are skipped, the frames decode to the split bytes);
     decompress_tensors_device gives the tensors back.
     What the split is for: interleaved, the exponent byte of a float is hidden from a byte-oriented parser and from huff0 — bf16 or
-    fp32 weights come out of compress_stream_device at their own size — and in a plane of its own it has under 3 bits.  fp16 gains
-    nothing at these levels (its top byte holds 5.5 bits and the Huffman stage stores it raw).
+    fp32 weights come out of compress_stream_device at their own size — and in a plane of its own it has under 3 bits.  With byte
+    planes fp16 gains nothing at these levels (its top byte holds 5.5 bits and the Huffman stage stores it raw).
+    planes="bits" (opt-in; the default and every call without it produce the same stream bytes as before): EVERY tensor, element
+    size 1 included (a bool mask holds one used bit of eight), goes through one split_bit_planes_device launch with
+    _plane_elem_size(t) and gets an "LZT2" header (LizardGPU_tensorHeaderWrite2, filter LIZARDGPU_FILTER_BIT_PLANES), which readers
+    of "LZT1" refuse.  A nearly constant bit plane is a long run that the LZ parser alone removes: fp16 weights shrink at all
+    (0.94 of raw), and bf16 / fp32 weights reach level 30's ratio at level 10 (0.76 against 0.84 for bf16).  Bit planes lose
+    against byte planes for activation-like bf16 (randn * 1.0) and for bf16 / fp32 weights at levels 30 and above: include/lizard_amd.h
+    has the table.  planes="bits" with split=False, or another value of `planes`, raises ValueError.
     In this order: one split launch (split_planes_device) for the tensors whose element size is above 1 — none with split=False,
     which compresses every tensor's own bytes and records element size 1 —, one batch of LizardGPU_compressFrames_device over all
     tensors, all headers written into one host buffer and uploaded with one copy, one torch.cat.  No payload byte crosses PCIe.
     Memory: the split bytes are a temporary of the size of the batch (beside the frames' LizardGPU_compressFrameBound regions)."""
     import torch
     L = _lib.lib()
+    if planes not in ("bytes", "bits"):
+        raise ValueError(f"compress_tensors_device: planes={planes!r} is neither 'bytes' nor 'bits'")
+    if planes == "bits" and not split:
+        raise ValueError("compress_tensors_device: planes='bits' with split=False (bit planes are a split)")
+    bits = planes == "bits"
     tensors = list(tensors)
     if not tensors:
         raise ValueError("compress_tensors_device: no tensors")
@@ -580,21 +620,24 @@ def compress_tensors_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, c
             raise _lib.LizardAmdError(f"compress_tensors_device: tensor {i}: {t.dim()} dimensions / dtype {name.decode()} do not fit a tensor header")
         d = _TensorDesc()
         d.elemSize, d.ndim, d.nbytes, d.dtype = (_plane_elem_size(t) if split else 1), t.dim(), int(t.numel()) * t.element_size(), name
+        d.filter = FILTER_BIT_PLANES if bits else FILTER_BYTE_PLANES
         for k, s in enumerate(t.shape):
             d.shape[k] = int(s)
         descs.append(d)
     raw = [_as_bytes(t) for t in tensors]
     wide = [i for i, d in enumerate(descs) if d.elemSize > 1]
-    if wide:
+    if bits:
+        raw = split_bit_planes_device(raw, [d.elemSize for d in descs])
+    elif wide:
         for i, p in zip(wide, split_planes_device([raw[i] for i in wide], [descs[i].elemSize for i in wide])):
             raw[i] = p
     frames = _compress_frames_device(raw, level, block_size_id, checksum, True, STREAM_FRAME_SLACK)
     host = np.zeros(len(descs) * TENSOR_HEADER_MAX, dtype=np.uint8)
     at, spans = 0, []
     for i, d in enumerate(descs):
-        n = L.LizardGPU_tensorHeaderWrite(host.ctypes.data + at, host.size - at, ctypes.byref(d))
+        n = L.LizardGPU_tensorHeaderWrite2(host.ctypes.data + at, host.size - at, ctypes.byref(d))
         if not n:
-            raise _lib.LizardAmdError(f"compress_tensors_device: tensor {i}: LizardGPU_tensorHeaderWrite refused the descriptor")
+            raise _lib.LizardAmdError(f"compress_tensors_device: tensor {i}: LizardGPU_tensorHeaderWrite2 refused the descriptor")
         spans.append((at, at + n))
         at += n
     headers = torch.from_numpy(host[:at]).to(device)
@@ -624,7 +667,7 @@ def _tensor_stream_index(src, what):
     out, at = [], 0
     for k, ((h, f), n) in enumerate(zip(pairs, takes)):
         d, used = _TensorDesc(), ctypes.c_size_t(0)
-        rc = L.LizardGPU_tensorHeaderRead(host.ctypes.data + at, n, ctypes.byref(d), ctypes.byref(used))
+        rc = L.LizardGPU_tensorHeaderRead2(host.ctypes.data + at, n, ctypes.byref(d), ctypes.byref(used))
         if rc or used.value != h["frame_bytes"]:
             raise _lib.LizardAmdError(f"{what}: tensor {k}: the skippable frame at offset {h['offset']} in front of the data frame is not a "
                                       f"tensor header, so the data frame at offset {f['offset']} has no tensor header in front of it")
@@ -635,10 +678,11 @@ def _tensor_stream_index(src, what):
 
 def tensors_info_device(stream):
     """What the tensor stream in `stream` (a contiguous uint8 CUDA tensor, what compress_tensors_device returns) holds, without
-    decoding anything: one dict per tensor with dtype (its name), shape, elem_size (of the split; 1 = stored unsplit), nbytes,
-    offset (of the tensor's header in the stream), header_bytes and frame_bytes (of the data frame behind the header).  Raises
+    decoding anything: one dict per tensor with dtype (its name), shape, planes ("bytes" or "bits": the filter), elem_size (of the
+    split; with "bytes", 1 = stored unsplit), nbytes, offset (of the tensor's header in the stream), header_bytes and frame_bytes (of the data frame behind the header).  Raises
     LizardAmdError naming the tensor's index for a data frame without a tensor header in front of it."""
-    return [{"dtype": d.dtype.decode(), "shape": tuple(int(s) for s in d.shape[:d.ndim]), "elem_size": int(d.elemSize), "nbytes": int(d.nbytes),
+    return [{"dtype": d.dtype.decode(), "shape": tuple(int(s) for s in d.shape[:d.ndim]), "planes": _PLANES_NAMES[int(d.filter)],
+             "elem_size": int(d.elemSize), "nbytes": int(d.nbytes),
              "offset": h["offset"], "header_bytes": h["frame_bytes"], "frame_bytes": f["frame_bytes"]}
             for h, f, d in _tensor_stream_index(stream, "tensors_info_device")]
 
@@ -647,8 +691,9 @@ def decompress_tensors_device(stream, verify_checksum=True):
     """The tensors of the tensor stream in `stream`, a contiguous uint8 CUDA tensor (what compress_tensors_device returns), with dtype
     and shape restored: a list of views into ONE allocation, each 256-byte aligned.  In this order: one stream_info_device, one
     indexed read of all header bytes, one decompress_stream_device — ONE decode batch for a stream of this library, because the headers
-    are skippable frames and every data frame carries its content size — and one join launch (join_planes_device).  No payload byte
-    crosses PCIe.
+    are skippable frames and every data frame carries its content size — and one join launch per filter that occurs in the stream
+    (byte planes, bit planes: a stream may mix both kinds of tensor), at most two, into the one result.  No payload byte crosses
+    PCIe.
     Raises LizardAmdError naming the index of the offending tensor when a data frame has no tensor header in front of it (or a
     skippable frame that is none), when a header's nbytes differs from its frame's decoded size (a data frame with records must
     carry its content size), when the shape does not make nbytes, or when torch does not know the dtype's name; a frame the decoder
@@ -681,5 +726,5 @@ def decompress_tensors_device(stream, verify_checksum=True):
     for _, _, d in entries:
         pieces.append(decoded[pos:pos + int(d.nbytes)])
         pos += int(d.nbytes)
-    joined = join_planes_device(pieces, [int(d.elemSize) for _, _, d in entries])
+    joined = _planes_device(pieces, [int(d.elemSize) for _, _, d in entries], True, [int(d.filter) for _, _, d in entries])
     return [b.view(dt).reshape(tuple(int(s) for s in d.shape[:d.ndim])) for b, dt, (_, _, d) in zip(joined, dtypes, entries)]

@@ -25,6 +25,7 @@
 #include "unframes_kernels.h"  // a batch of frames walked, decoded and settled in device memory (LizardGPU_decompressFrames_device)
 #include "unstream_kernels.h"  // the walk across the frames of a stream in device memory (LizardGPU_decompressStream_device)
 #include "planes_kernels.h"    // the bytes of a batch of buffers split into planes and joined again (LizardGPU_splitPlanes_device)
+#include "bitplanes_kernels.h" // ... and their bits (LizardGPU_splitBitPlanes_device)
 
 namespace {
 
@@ -887,15 +888,16 @@ int   lzk_unstream_walk_launch(const void* d_src, size_t srcSize, LzStreamCtl* d
     LZ_HIP(hipGetLastError());
     return 0;
 }
-int   lzk_planes_launch(LzCtx* c, const LzPlanesEntry* d_tab, uint32_t nEntries, uint32_t nTiles, int join, hipStream_t stream)
+int   lzk_planes_launch(LzCtx* c, const LzPlanesEntry* d_tab, uint32_t nEntries, uint32_t nTiles, int join, int bits, hipStream_t stream)
 {
     static_assert(sizeof(LzPlanesEntry) == 32, "the table the host file fills");
     if (!d_tab || nEntries == 0 || nTiles == 0) { snprintf(t_err, sizeof t_err, "bad argument (null pointer or no tiles)"); return -LIZARDGPU_ERR_ARG; }
     // a wave per tile up to eight waves per SIMD, a grid stride over the rest
     const u32 groups = (nTiles + LZP_WAVES - 1u) / LZP_WAVES, cap = (u32)c->cus * 8u;
     const dim3 grid(groups < cap ? groups : cap), block(64 * LZP_WAVES);
-    if (join) hipLaunchKernelGGL(lz_planes_join_kernel, grid, block, 0, stream, d_tab, nEntries, nTiles);
-    else hipLaunchKernelGGL(lz_planes_split_kernel, grid, block, 0, stream, d_tab, nEntries, nTiles);
+    void (*const kernel)(const LzPlanesEntry*, u32, u32) = bits ? (join ? lz_bitplanes_join_kernel : lz_bitplanes_split_kernel)
+                                                                : (join ? lz_planes_join_kernel : lz_planes_split_kernel);
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, d_tab, nEntries, nTiles);
     LZ_HIP(hipGetLastError());
     return 0;
 }

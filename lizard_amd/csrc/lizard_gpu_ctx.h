@@ -90,6 +90,7 @@ typedef struct LzCtx {
     unsigned long long devFramesDecodeStats[4];    /* LizardGPU_framesDecodeDeviceStats (lizard_unframes_device.c); since process start */
     unsigned long long devStreamDecodeStats[4];    /* LizardGPU_streamDecodeDeviceStats (lizard_unstream_device.c); since process start */
     unsigned long long devPlanesStats[4];          /* LizardGPU_planesStats (lizard_planes_device.c); since process start */
+    unsigned long long devBitPlanesStats[4];       /* LizardGPU_bitPlanesStats (lizard_planes_device.c); since process start */
     LzStage stage[LZ_STAGES];
     LzCombine comb;
     pthread_mutex_t mu;
@@ -195,10 +196,11 @@ int   lzk_unframes_finish_launch(const struct LzUnframesEntry* d_frames, uint32_
 struct LzStreamCtl;
 int   lzk_unstream_walk_launch(const void* d_src, size_t srcSize, struct LzStreamCtl* d_ctl, struct LzWalkResult* d_res, uint64_t* d_offs,
                                uint32_t tableCap, hipStream_t stream);
-/* LizardGPU_splitPlanes_device / LizardGPU_joinPlanes_device (lizard_planes_device.c, planes_kernels.h): the one launch over the
- * nTiles tiles of the batch's nEntries non-empty buffers, whose table lies at d_tab */
+/* LizardGPU_splitPlanes_device / LizardGPU_joinPlanes_device (lizard_planes_device.c, planes_kernels.h) and, with bits != 0,
+ * LizardGPU_splitBitPlanes_device / LizardGPU_joinBitPlanes_device (bitplanes_kernels.h): the one launch over the nTiles tiles of the
+ * batch's nEntries non-empty buffers, whose table lies at d_tab */
 struct LzPlanesEntry;
-int   lzk_planes_launch(LzCtx* c, const struct LzPlanesEntry* d_tab, uint32_t nEntries, uint32_t nTiles, int join, hipStream_t stream);
+int   lzk_planes_launch(LzCtx* c, const struct LzPlanesEntry* d_tab, uint32_t nEntries, uint32_t nTiles, int join, int bits, hipStream_t stream);
 /* lizard_pipeline_host.c: its staging helpers, shared with lizard_unframe_host.c */
 int    lzp_ensure_dev(LzCtx* c, void** p, size_t* cap, size_t need);
 int    lzp_ensure_pinned(void** p, size_t* cap, size_t need);

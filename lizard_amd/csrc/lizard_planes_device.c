@@ -1,7 +1,8 @@
 /* lizard_planes_device.c — LizardGPU_splitPlanes_device / LizardGPU_joinPlanes_device: the bytes of a batch of device buffers
- * regrouped by significance, and back, in ONE launch each (planes_kernels.h is the device side), and the tensor header — a
- * skippable frame that tells a reader of a stream which element size a frame's bytes were split with, and the tensor's dtype and
- * shape (include/lizard_amd.h Part 3c).  Plain C on the HIP runtime's C API and the shim of lizard_gpu_ctx.h, like the sibling
+ * regrouped by significance, and back, in ONE launch each (planes_kernels.h is the device side); LizardGPU_splitBitPlanes_device /
+ * LizardGPU_joinBitPlanes_device: the same call with their bits regrouped by weight (bitplanes_kernels.h); and the tensor header — a
+ * skippable frame that tells a reader of a stream which filter and element size a frame's bytes were split with, and the tensor's
+ * dtype and shape (include/lizard_amd.h Part 3c).  Plain C on the HIP runtime's C API and the shim of lizard_gpu_ctx.h, like the sibling
  * device entries.
  *
  * A call: the arguments are checked before anything is touched; the non-empty buffers become the entries of a table, each with
@@ -19,7 +20,7 @@
 #include "lizard_device_common.h"
 #include "planes_kernels.h"
 
-static int planes_locked(LzCtx* c, const LzPlanesEntry* tab, size_t nEntries, uint32_t nTiles, int join, hipStream_t stream)
+static int planes_locked(LzCtx* c, const LzPlanesEntry* tab, size_t nEntries, uint32_t nTiles, int join, int bits, hipStream_t stream)
 {
     LzStage* s = c->stage;
     const size_t bytes = nEntries * sizeof(LzPlanesEntry);
@@ -30,13 +31,15 @@ static int planes_locked(LzCtx* c, const LzPlanesEntry* tab, size_t nEntries, ui
     memcpy(s[0].h_aux, tab, bytes);
     c->hostKernelMs = -1.0f;
     LZ_HIP(hipMemcpyAsync(c->dfTab, s[0].h_aux, bytes, hipMemcpyHostToDevice, stream));
-    if ((rc = lzk_planes_launch(c, (const LzPlanesEntry*)c->dfTab, (uint32_t)nEntries, nTiles, join, stream))) return rc;
+    if ((rc = lzk_planes_launch(c, (const LzPlanesEntry*)c->dfTab, (uint32_t)nEntries, nTiles, join, bits, stream))) return rc;
     LZ_HIP(hipStreamSynchronize(stream));
     return 0;
 }
 
+/* bits: 0 = byte planes, 1 = bit planes.  The checks, the tiles and the table are the same for both; the kernel and the counters
+ * differ. */
 static int planes(size_t nBuffers, void* const* d_dsts, const void* const* d_srcs, const size_t* sizes, const uint32_t* elemSizes,
-                  int join, hipStream_t stream)
+                  int join, int bits, hipStream_t stream)
 {
     LzPlanesEntry* tab;
     LzGuard g;
@@ -71,7 +74,7 @@ static int planes(size_t nBuffers, void* const* d_dsts, const void* const* d_src
     }
     lzk_guard_acquire(&g);
     if (g.rc) { free(tab); return g.rc; }
-    rc = planes_locked(g.c, tab, live, (uint32_t)tiles, join, stream);
+    rc = planes_locked(g.c, tab, live, (uint32_t)tiles, join, bits, stream);
     if (rc) {                                                  /* nothing of this call stays in flight; the error text survives */
         char keep[LZK_ERR_BYTES];
         lz_err_save(keep);
@@ -79,9 +82,10 @@ static int planes(size_t nBuffers, void* const* d_dsts, const void* const* d_src
         (void)hipGetLastError();
         lz_err_restore(keep);
     } else {
-        g.c->devPlanesStats[join ? 1 : 0] += nBuffers;
-        g.c->devPlanesStats[2] += bytes;
-        g.c->devPlanesStats[3]++;
+        unsigned long long* const st = bits ? g.c->devBitPlanesStats : g.c->devPlanesStats;
+        st[join ? 1 : 0] += nBuffers;
+        st[2] += bytes;
+        st[3]++;
     }
     lzk_guard_release(&g);
     free(tab);
@@ -91,18 +95,35 @@ static int planes(size_t nBuffers, void* const* d_dsts, const void* const* d_src
 int LizardGPU_splitPlanes_device(size_t nBuffers, void* const* d_dsts, const void* const* d_srcs, const size_t* sizes,
                                  const uint32_t* elemSizes, void* stream)
 {
-    return planes(nBuffers, d_dsts, d_srcs, sizes, elemSizes, 0, (hipStream_t)stream);
+    return planes(nBuffers, d_dsts, d_srcs, sizes, elemSizes, 0, 0, (hipStream_t)stream);
 }
 
 int LizardGPU_joinPlanes_device(size_t nBuffers, void* const* d_dsts, const void* const* d_srcs, const size_t* sizes,
                                 const uint32_t* elemSizes, void* stream)
 {
-    return planes(nBuffers, d_dsts, d_srcs, sizes, elemSizes, 1, (hipStream_t)stream);
+    return planes(nBuffers, d_dsts, d_srcs, sizes, elemSizes, 1, 0, (hipStream_t)stream);
 }
 
 int LizardGPU_planesStats(unsigned long long out[4])
 {
     return lz_stats_read(out, offsetof(LzCtx, devPlanesStats));
+}
+
+int LizardGPU_splitBitPlanes_device(size_t nBuffers, void* const* d_dsts, const void* const* d_srcs, const size_t* sizes,
+                                    const uint32_t* elemSizes, void* stream)
+{
+    return planes(nBuffers, d_dsts, d_srcs, sizes, elemSizes, 0, 1, (hipStream_t)stream);
+}
+
+int LizardGPU_joinBitPlanes_device(size_t nBuffers, void* const* d_dsts, const void* const* d_srcs, const size_t* sizes,
+                                   const uint32_t* elemSizes, void* stream)
+{
+    return planes(nBuffers, d_dsts, d_srcs, sizes, elemSizes, 1, 1, (hipStream_t)stream);
+}
+
+int LizardGPU_bitPlanesStats(unsigned long long out[4])
+{
+    return lz_stats_read(out, offsetof(LzCtx, devBitPlanesStats));
 }
 
 /* ---- the tensor header: host code, no device ---- */
@@ -112,18 +133,21 @@ static void put_le(uint8_t* p, uint64_t v, int n) { int i; for (i = 0; i < n; i+
 static uint64_t get_le(const uint8_t* p, int n) { uint64_t v = 0; int i; for (i = 0; i < n; i++) v |= (uint64_t)p[i] << (8 * i); return v; }
 static int elem_ok(uint32_t e) { return e == 1 || e == 2 || e == 4 || e == 8; }
 
-size_t LizardGPU_tensorHeaderWrite(void* dst, size_t dstCapacity, const LizardGPU_tensorDesc_t* desc)
+/* Both versions: the v1 fields of the descriptor and the filter.  "LZT1" is filter 0 with zero pad bytes; "LZT2" holds the filter
+ * in payload byte 6 and is written for a filter other than 0 only, so that every meaning has one encoding. */
+static size_t header_write(void* dst, size_t dstCapacity, const LizardGPU_tensorDesc_t* desc, uint32_t filter)
 {
     uint8_t* p = (uint8_t*)dst;
     size_t total;
     uint32_t i;
     if (!dst || !desc || !elem_ok(desc->elemSize) || desc->ndim > 8 || !memchr(desc->dtype, 0, sizeof desc->dtype)) return 0;
+    if (filter != LIZARDGPU_FILTER_BYTE_PLANES && filter != LIZARDGPU_FILTER_BIT_PLANES) return 0;
     total = 8 + LZT_FIXED + 8 * (size_t)desc->ndim;
     if (dstCapacity < total) return 0;
     put_le(p, LIZARDGPU_TENSOR_MAGIC, 4);
     put_le(p + 4, total - 8, 4);
-    memcpy(p + 8, "LZT1", 4);
-    p[12] = (uint8_t)desc->elemSize; p[13] = (uint8_t)desc->ndim; p[14] = p[15] = 0;
+    memcpy(p + 8, filter ? "LZT2" : "LZT1", 4);
+    p[12] = (uint8_t)desc->elemSize; p[13] = (uint8_t)desc->ndim; p[14] = (uint8_t)filter; p[15] = 0;
     put_le(p + 16, desc->nbytes, 8);
     memset(p + 24, 0, 24);
     memcpy(p + 24, desc->dtype, strlen(desc->dtype));
@@ -131,9 +155,24 @@ size_t LizardGPU_tensorHeaderWrite(void* dst, size_t dstCapacity, const LizardGP
     return total;
 }
 
-int LizardGPU_tensorHeaderRead(const void* src, size_t srcSize, LizardGPU_tensorDesc_t* desc, size_t* headerBytes)
+size_t LizardGPU_tensorHeaderWrite(void* dst, size_t dstCapacity, const LizardGPU_tensorDesc_t* desc)
+{
+    return header_write(dst, dstCapacity, desc, LIZARDGPU_FILTER_BYTE_PLANES);
+}
+
+size_t LizardGPU_tensorHeaderWrite2(void* dst, size_t dstCapacity, const LizardGPU_tensorDesc2_t* desc)
+{
+    LizardGPU_tensorDesc_t v1;
+    if (!desc) return 0;
+    memcpy(&v1, desc, sizeof v1);                              /* the v1 fields come first */
+    return header_write(dst, dstCapacity, &v1, desc->filter);
+}
+
+/* v2 == 0: the v1 reader, which knows "LZT1" only.  *filter is written together with *desc. */
+static int header_read(const void* src, size_t srcSize, LizardGPU_tensorDesc_t* desc, uint32_t* filter, size_t* headerBytes, int v2)
 {
     const uint8_t* p = (const uint8_t*)src;
+    int bits = 0;
     const int unknown = -(int)LIZARDGPU_FRAME_ERR_frameType_unknown, incomplete = -(int)LIZARDGPU_FRAME_ERR_frameHeader_incomplete;
     uint64_t len;
     uint32_t ndim, i;
@@ -146,10 +185,13 @@ int LizardGPU_tensorHeaderRead(const void* src, size_t srcSize, LizardGPU_tensor
     len = get_le(p + 4, 4);
     if (len < LZT_FIXED || len > LZT_FIXED + 64 || (len - LZT_FIXED) % 8) return unknown;
     ndim = (uint32_t)(len - LZT_FIXED) / 8;
-    if (srcSize >= 12 && memcmp(p + 8, "LZT1", 4)) return unknown;
+    if (srcSize >= 12) {
+        bits = v2 && !memcmp(p + 8, "LZT2", 4);
+        if (!bits && memcmp(p + 8, "LZT1", 4)) return unknown;
+    }
     if (srcSize >= 13 && !elem_ok(p[12])) return unknown;
     if (srcSize >= 14 && p[13] != ndim) return unknown;
-    if (srcSize >= 15 && p[14]) return unknown;
+    if (srcSize >= 15 && p[14] != (bits ? LIZARDGPU_FILTER_BIT_PLANES : 0)) return unknown;
     if (srcSize >= 16 && p[15]) return unknown;
     if (srcSize >= 48 && !memchr(p + 24, 0, 24)) return unknown;
     if (srcSize < 8 + len) return incomplete;
@@ -159,6 +201,24 @@ int LizardGPU_tensorHeaderRead(const void* src, size_t srcSize, LizardGPU_tensor
         memcpy(desc->dtype, p + 24, 24);
         for (i = 0; i < ndim; i++) desc->shape[i] = get_le(p + 8 + LZT_FIXED + 8 * i, 8);
     }
+    if (filter) *filter = bits ? LIZARDGPU_FILTER_BIT_PLANES : LIZARDGPU_FILTER_BYTE_PLANES;
     if (headerBytes) *headerBytes = (size_t)(8 + len);
     return 0;
+}
+
+int LizardGPU_tensorHeaderRead(const void* src, size_t srcSize, LizardGPU_tensorDesc_t* desc, size_t* headerBytes)
+{
+    return header_read(src, srcSize, desc, NULL, headerBytes, 0);
+}
+
+int LizardGPU_tensorHeaderRead2(const void* src, size_t srcSize, LizardGPU_tensorDesc2_t* desc, size_t* headerBytes)
+{
+    LizardGPU_tensorDesc_t v1;
+    uint32_t filter = 0;
+    const int rc = header_read(src, srcSize, &v1, &filter, headerBytes, 1);
+    if (!rc && desc) {
+        memcpy(desc, &v1, sizeof v1);
+        desc->filter = filter; desc->reserved = 0;
+    }
+    return rc;
 }

@@ -128,17 +128,24 @@ LZ_DEV void lzp_move(const u8* src, u8* dst, u64 n, u64 e0, u64 e1)
     }
 }
 
+// The buffer of tile `tile` (wave-uniform, < the batch's tile count): the last entry whose firstTile <= tile.  Shared with
+// bitplanes_kernels.h.
+LZ_DEV const LzPlanesEntry* lzp_entry_of(const LzPlanesEntry* tab, u32 nEntries, u32 tile)
+{
+    u32 lo = 0, hi = nEntries;
+    while (hi - lo > 1) {
+        const u32 mid = lo + (hi - lo) / 2;
+        if (tab[mid].firstTile <= tile) lo = mid; else hi = mid;
+    }
+    return tab + lo;
+}
+
 // Tile `tile` (< the batch's tile count) of the batch: all lanes of one wave call; everything but the lane's share is wave-uniform.
 template <bool JOIN>
 LZ_DEV void lz_planes_tile(const LzPlanesEntry* tab, u32 nEntries, u32 tileOfWave)
 {
     const u32 tile = lz_uniform(tileOfWave);                       // in SGPRs: the bisection and the entry are scalar loads
-    u32 lo = 0, hi = nEntries;                                     // the last entry whose firstTile <= tile
-    while (hi - lo > 1) {
-        const u32 mid = lo + (hi - lo) / 2;
-        if (tab[mid].firstTile <= tile) lo = mid; else hi = mid;
-    }
-    const LzPlanesEntry* const e = tab + lo;
+    const LzPlanesEntry* const e = lzp_entry_of(tab, nEntries, tile);
     const u8* const src = (const u8*)(uintptr_t)e->src;
     u8* const dst = (u8*)(uintptr_t)e->dst;
     const u64 size = e->size;
