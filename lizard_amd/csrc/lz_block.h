@@ -33,6 +33,7 @@
 // in every lane (they are derived from ballots/readlanes and live in SGPRs).
 #pragma once
 #include "lz_wave.h"
+#include "lz_touch.h"
 #include "lz_huf.h"
 
 #define LZ_SUBBLOCK       (1u << 17)        // LIZARD_BLOCK_SIZE, reference lib/lizard_compress.h:122
@@ -55,6 +56,7 @@ struct LzStreams {
                                                         // store per sequence would sit in front of every later load wait
     u32 lastLits;                                       // uniform: trailing literals of the sub-block (fast.h:187-190)
     u32 sweepAt;                                        // uniform: position at which the table is swept next (tables with positions modulo a power of two)
+    u32 raAt, raEnd;                                    // uniform: the block's source read-ahead cursor and its end (lz_touch.h; level-10 producers only)
 #ifdef LZ_PROFILE
     u64 prof_last; u64 prof[16];                         // shader-clock deltas per phase (profile builds only)
 #endif
@@ -719,6 +721,13 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
     // lane 0.)  Where inside that slack a sweep runs changes no decision: a slot older than 65535 is dead for the reference either way.
     constexpr bool kSweepMoved = LANEFORMS && TAB::kSweeps && LZ_TAIL_SWEEP;
     constexpr bool kBackLane = kLaneChain && LZ_LATCH_CHAIN;          // the chain pass on lane-prepared lengths, exits folded
+    // Source read-ahead (lz_touch.h): behind its table exchange every round asks, through the scalar path, for the source lines up to
+    // LZ_READAHEAD in front of its first position, LZ_RA_PER_ROUND of them at most, and consumes what the round before asked for —
+    // the exchange's own lgkmcnt(0) has covered those, and the new ones have a whole round until the next one.  (Asked for at the HEAD
+    // of the round they would stand in front of that same wait.)  What it takes off the round: the count trip behind an unresolved
+    // length and the load of the next round's bytes find their lines in L2 instead of fetching them from HBM through the in-order queue.
+    constexpr bool kReadAhead = LANEFORMS && TAB::kXchg && LZ_SRC_READAHEAD;
+    LzTouched raVal[LZ_RA_PER_ROUND] = {};                            // uniform: what the round before was handed by its touches
     const u32 lane = lz_lane();
     const u64 laneBit = 1ull << lane;
     const u64 lanesBelow = laneBit - 1ull;
@@ -790,6 +799,14 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
             // slot are served in lane order, so each gets back what the reference's serial walk would have found there.
             // Visits after the winner never happened: they are taken back once the winner is known (below).
             e = table.xchg(valid ? h : (1u << HASHLOG), mine);
+            if constexpr (kReadAhead) {
+                for (u32 k = 0; k < LZ_RA_PER_ROUND; k++) lz_touch_use(raVal[k]);
+                const u32 p0 = lz_readlane(p, 0);
+                const u32 raLim = p0 + LZ_READAHEAD < st.raEnd ? p0 + LZ_READAHEAD : st.raEnd;
+                lz_touch_round(src, p0);
+                for (u32 k = 0; k < LZ_RA_PER_ROUND; k++)
+                    if (st.raAt < raLim) { raVal[k] = lz_touch(src, st.raAt + LZ_RA_AT); st.raAt += LZ_RA_LINE; }
+            }
         } else {
         e = table.get(h, p);                                         // value before this round
         bool lost;
@@ -964,8 +981,16 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
             continue;
         }
         // ---------------- extend ----------------
+#ifdef LZ_PROFILE
+        // (profile builds, level-10 producers) the count trips apart from the rest of the extension: slot 4 their clocks, slot 14 how
+        // many were taken, slot 12 the rounds with a winner — trips per round and clocks per trip in profiles/source_readahead_ab.txt
+        if constexpr (LANEFORMS) { LZ_PROF(st, 2); st.prof[12]++; if (ml == 0xFFFFu) st.prof[14]++; if (back == 0xFFFFu) st.prof[14]++; }
+#endif
         if (ml == 0xFFFFu) ml = 4u + lz_count_fwd(src, P + 4u, M + 4u, matchlimit);            // fast.h:100
         if (back == 0xFFFFu) back = lz_count_back(src, P, M, anchor);                           // fast.h:102
+#ifdef LZ_PROFILE
+        if constexpr (LANEFORMS) LZ_PROF(st, 4);
+#endif
         if constexpr (TAB::kSweeps) {
             // A match moves ip by up to a sub-block at once (128 KiB - 1), four sweep intervals of the 17-bit table, and the round's
             // own check below only sweeps once, at the position it finds itself at: a slot stamped "65536 old" by the last sweep would

@@ -100,6 +100,7 @@ LZ_DEV void lz_split_producer(const LzSplitArgs& a, const LzSplitShared& sh, u32
         const u8* src = a.src + (a.srcOffsets ? lz_uniform64(a.srcOffsets[b]) : (u64)b * a.blockSize);
         const u32 cons = lz_lds_claim(sh.nextCons) % a.nCons;                  // the block's consumer
         lz_tab_fresh<HASHLOG>(tab); st.sweepAt = LzTab::kSweepEvery;
+        if constexpr (LANEFORMS && LZ_SRC_READAHEAD) lz_touch_begin(src, n, st.raAt, st.raEnd);      // one cursor per block, carried across its sub-blocks
         lz_lds_sync();
         for (u32 pos = 0; pos < n; ) {                                           // (n >= 1: the launcher refuses empty blocks)
             const u32 part = (n - pos) < LZ_SUBBLOCK ? (n - pos) : LZ_SUBBLOCK;
