@@ -12,7 +12,9 @@
  *                                                               (a whole frame in one call on the GPU: LizardGPU_decompressFrame, Part 3b)
  *   Part 1d  XXH32 / XXH64          lib/xxhash/xxhash.h         (XXH_NAMESPACE=Lizard_, lib/Makefile:52)
  *   Part 2   batch extension (ours): many independent blocks per call, host- or device-resident, several GPUs, decompression
- *   Part 3   the strict frame twins of rounds 2-3 (LizardGPU_compressFrame ...)
+ *   Part 3   the strict frame twins of rounds 2-3 (LizardGPU_compressFrame ...) and their forms for data in device memory: one frame
+ *            (LizardGPU_compressFrame_device), a batch (LizardGPU_compressFrames_device), a batch written back to back into one
+ *            buffer, a .liz stream (LizardGPU_compressStream_device, LizardGPU_compressStreamBound)
  *   Part 3b  whole-frame decompression on the GPU (LizardGPU_decompressFrame, LizardGPU_decompressFrame_device,
  *            LizardGPU_decompressFrames_device, LizardGPU_decompressStream_device ...)
  *   Part 3c  tensor streams: element bytes split into planes before compressing (LizardGPU_splitPlanes_device,
@@ -472,6 +474,41 @@ int    LizardGPU_frameCompressDeviceStats(unsigned long long out[4]);
  * LizardGPU_frameCompressDeviceStats counts this entry's blocks and chunks in [0], [1], [2]; it never adds to [3]. */
 int    LizardGPU_compressFrames_device(size_t nFrames, void* const* d_dsts, const size_t* dstCapacities, const void* const* d_srcs,
                                        const size_t* srcSizes, size_t* results, const LizardGPU_framePrefs_t* preferencesPtr, void* stream);
+
+/* ---- many buffers in device memory, one frame each, BACK TO BACK in one device buffer: a .liz stream written in one call ----
+ * The writing half of LizardGPU_decompressStream_device.  d_srcs, srcSizes, prefixes, prefixSizes and frameOffsets are HOST arrays;
+ * d_srcs[i] and d_dst are device pointers on the selected device, prefixes[i] points to prefixSizes[i] bytes in HOST memory
+ * (prefixes == prefixSizes == NULL: no prefixes).  d_dst[0 .. returned size) is, for i = 0 .. nFrames - 1, prefixes[i][0 ..
+ * prefixSizes[i]) followed by frame i.  A prefix is opaque to this entry: a tensor stream passes its skippable tensor headers.
+ * Frame i is byte for byte what LizardGPU_compressFrame_device writes for d_srcs[i], srcSizes[i], the same prefs and a capacity of
+ * LizardGPU_compressFrameBound(srcSizes[i], prefs) + 8: the level clamp, the block size id shrunk to EACH frame's own input,
+ * contentSize != 0 meaning "write this frame's srcSize", srcSize == 0, a 1-byte last block.  frameOffsets (may be NULL, else
+ * nFrames + 1 entries): frameOffsets[i] is where prefix i starts, frameOffsets[nFrames] the returned size.
+ * Returns the stream's size or a code LizardGPU_frameIsError recognises:
+ *   - a frame the single-frame entry would refuse up front (level without a kernel, linked mode above one block, skippable frame
+ *     type, block size id out of range, a null source with a non-zero size, a null prefix with a non-zero size) is refused BEFORE
+ *     anything is launched: that frame's code, *failedFrame (may be NULL) its index, d_dst untouched.  The first such frame in index
+ *     order decides: a stream with a hole is not a stream.
+ *   - dstMaxSize_tooSmall when the stream does not fit dstCapacity; nothing outside d_dst[0 .. dstCapacity) is written, and what
+ *     d_dst holds is unspecified.  LizardGPU_compressStreamBound bytes never get this answer: that is the sum of the prefix sizes and
+ *     of every frame's LizardGPU_compressFrameBound + 8, so the bound's known 5-byte shortfall is covered.
+ *   - GENERIC for a null array with nFrames > 0, for 2^32 blocks or more, and when the machinery fails (no device, HIP, allocation);
+ *     LizardGPU_lastError has the text.  Never a host fall-back.
+ * nFrames == 0 returns 0 and touches nothing.  Nothing outside d_srcs[i][0 .. srcSizes[i]) is read; sources may start at any byte
+ * address.  SYNCHRONOUS like its siblings: ordered after what `stream` holds at the call; on return the stream is visible to work
+ * enqueued on `stream` afterwards.
+ * The blocks of all frames form one list that is compressed in chunks as in LizardGPU_compressFrames_device (the same
+ * LIZARDGPU_FRAME_CHUNK_BLOCKS); where a record goes is the host's sum of everything in front of it that does not depend on
+ * compressed sizes plus a prefix sum of record sizes that the device carries from chunk to chunk, so the host waits once per call.
+ * NO payload byte crosses PCIe: the tables and the prefix bytes go up in one copy, 16 bytes (and the offsets, when asked for) come
+ * down.  The content checksums are computed on the device as in LizardGPU_compressFrames_device.
+ * LizardGPU_streamCompressDeviceStats, since process start, selected device: [0] frames written, [1] blocks stored raw, [2] chunks
+ * launched, [3] calls that launched anything.  This entry adds nothing to LizardGPU_frameCompressDeviceStats. */
+size_t LizardGPU_compressStreamBound(size_t nFrames, const size_t* srcSizes, const size_t* prefixSizes, const LizardGPU_framePrefs_t* prefs);
+size_t LizardGPU_compressStream_device(void* d_dst, size_t dstCapacity, size_t nFrames, const void* const* d_srcs, const size_t* srcSizes,
+                                       const void* const* prefixes, const size_t* prefixSizes, const LizardGPU_framePrefs_t* prefs,
+                                       uint64_t* frameOffsets, size_t* failedFrame, void* stream);
+int    LizardGPU_streamCompressDeviceStats(unsigned long long out[4]);
 
 /* Streaming form.  LizardGPU_cctx_t replaces LizardF_compressionContext_t (lib/lizard_frame.h:145); the functions
  * replace LizardF_createCompressionContext / _freeCompressionContext (:157-158, int result: 0 or -LIZARDGPU_FRAME_ERR_*),

@@ -100,6 +100,12 @@ def lib():
     L.LizardGPU_frameCompressDeviceStats.argtypes = [c.c_void_p]; L.LizardGPU_frameCompressDeviceStats.restype = c.c_int
     L.LizardGPU_compressFrames_device.argtypes = [c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
     L.LizardGPU_compressFrames_device.restype = c.c_int
+    L.LizardGPU_compressStreamBound.argtypes = [c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p]
+    L.LizardGPU_compressStreamBound.restype = c.c_size_t
+    L.LizardGPU_compressStream_device.argtypes = [c.c_void_p, c.c_size_t, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                  c.c_void_p, c.c_void_p, c.c_void_p]
+    L.LizardGPU_compressStream_device.restype = c.c_size_t
+    L.LizardGPU_streamCompressDeviceStats.argtypes = [c.c_void_p]; L.LizardGPU_streamCompressDeviceStats.restype = c.c_int
     L.LizardGPU_decompressFrames_device.argtypes = [c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint,
                                                     c.c_void_p]
     L.LizardGPU_decompressFrames_device.restype = c.c_int

@@ -413,20 +413,84 @@ def decompress_frames_device(frames, sizes=None, verify_checksum=True):
 STREAM_FRAME_SLACK = 8          # bytes compress_stream_device gives every frame beyond LizardGPU_compressFrameBound (5 are needed)
 
 
-def compress_stream_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksum=False):
-    """A .liz STREAM for `tensors`: compress_frames_device(..., content_size=True) — one frame per tensor, one batch — and one torch.cat
-    of the frame views (torch plumbing, no kernel of its own).  Returns one uint8 CUDA tensor: the frames back to back, which the
-    reference's decoder reads frame after frame and decompress_stream_device decodes in ONE batch, because every header says how
-    many bytes its frame decodes to.
-    Every frame gets STREAM_FRAME_SLACK = 8 bytes of room more than LizardGPU_compressFrameBound (see the note at that function in
-    include/lizard_amd.h): a block of ONE byte makes a record with 6 bytes of payload,
-    5 more than the bound counts.  The 8 bytes a header without content size leaves unused hide that; a 15-byte header does not, so
-    with the bound alone a tensor of one byte — or one whose size is one more than a multiple of the block size — is refused."""
+def compress_stream_device_into(tensors, dst=None, prefixes=None, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksum=False, content_size=True):
+    """A .liz STREAM for `tensors` — contiguous uint8 CUDA tensors on one device, zero-length ones allowed — written into ONE uint8 CUDA
+    tensor in ONE call of LizardGPU_compressStream_device on torch's current stream: per tensor `prefixes[i]` (host bytes, opaque to
+    the entry; None: no prefixes) and then the frame compress_frame_device writes for tensor i with 8 bytes more than its
+    LizardGPU_compressFrameBound.  Where frame i starts is decided on the device, so every compressed byte is written once, to its
+    place, and no payload byte crosses PCIe, with or without `checksum`.  Without `dst` the output has
+    LizardGPU_compressStreamBound bytes — the only allocation of the call; a `dst` that is too small raises (dstMaxSize_tooSmall),
+    as does a tensor the single-frame entry would refuse, naming the first such tensor.  Returns (dst[:n], offsets): the stream, and
+    the n + 1 places where prefix 0, prefix 1, ... start and the stream ends."""
+    import torch
+    L = _lib.lib()
+    tensors = list(tensors)
+    if not tensors:
+        raise ValueError("compress_stream_device_into: no tensors")
+    device = tensors[0].device
+    for t in tensors:
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.device == device
+    n = len(tensors)
+    p = _FramePrefs()
+    p.frameInfo.blockSizeID = block_size_id
+    p.frameInfo.blockMode = 1
+    p.frameInfo.contentChecksumFlag = 1 if checksum else 0
+    p.frameInfo.contentSize = 1 if content_size else 0          # (non-zero: "write each frame's own size")
+    p.compressionLevel = level
+    sizes = (ctypes.c_size_t * n)(*[int(t.numel()) for t in tensors])
+    srcs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors])
+    pre_ptrs = pre_sizes = blob = None
+    if prefixes is not None:
+        prefixes = [bytes(x) for x in prefixes]
+        assert len(prefixes) == n
+        blob = np.frombuffer(b"".join(prefixes) + b"\0", dtype=np.uint8)    # (kept alive until the call returns)
+        pre_sizes = (ctypes.c_size_t * n)(*[len(x) for x in prefixes])
+        at, ptrs = 0, []
+        for x in prefixes:
+            ptrs.append(blob.ctypes.data + at)
+            at += len(x)
+        pre_ptrs = (ctypes.c_void_p * n)(*ptrs)
+    if dst is None:
+        cap = _lib.check_frame(L.LizardGPU_compressStreamBound(n, sizes, pre_sizes, ctypes.byref(p)), "LizardGPU_compressStreamBound")
+        dst = torch.empty(cap, dtype=torch.uint8, device=device)
+    assert dst.is_cuda and dst.dtype == torch.uint8 and dst.is_contiguous() and dst.device == device
+    offsets = (ctypes.c_uint64 * (n + 1))()
+    failed = ctypes.c_size_t(0)
+    L.LizardGPU_setDevice(device.index or 0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    r = L.LizardGPU_compressStream_device(dst.data_ptr(), int(dst.numel()), n, srcs, sizes, pre_ptrs, pre_sizes, ctypes.byref(p), offsets,
+                                          ctypes.byref(failed), stream)
+    if L.LizardGPU_frameIsError(r):
+        raise _lib.LizardAmdError(f"LizardGPU_compressStream_device: {L.LizardF_getErrorName(r).decode()} "
+                                  f"{L.LizardGPU_lastError().decode(errors='replace')}".strip())
+    return dst[:r], [int(o) for o in offsets]
+
+
+def _compress_stream_device_cat(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksum=False):
+    """compress_stream_device as it was before LizardGPU_compressStream_device: compress_frames_device(..., content_size=True) with
+    STREAM_FRAME_SLACK bytes of room behind every frame's bound, and one torch.cat of the frame views.  Kept as the yardstick of the
+    tests and of scripts/stream_compress_device_bench.py: the same bytes, every one of them written twice."""
     import torch
     frames = _compress_frames_device(tensors, level, block_size_id, checksum, True, STREAM_FRAME_SLACK)
     if not frames:
         raise ValueError("compress_stream_device: no tensors")
     return torch.cat(frames)
+
+
+def compress_stream_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksum=False):
+    """A .liz STREAM for `tensors`: one frame with content size per tensor, back to back, in ONE call of
+    LizardGPU_compressStream_device (compress_stream_device_into without prefixes) into ONE allocation of
+    LizardGPU_compressStreamBound bytes.  Returns one uint8 CUDA tensor, a view of that allocation: the frames, which the
+    reference's decoder reads frame after frame and decompress_stream_device decodes in ONE batch, because every header says how
+    many bytes its frame decodes to.
+    Every frame gets STREAM_FRAME_SLACK = 8 bytes of room more than LizardGPU_compressFrameBound (see the note at that function in
+    include/lizard_amd.h; the stream bound counts them): a block of ONE byte makes a record with 6 bytes of payload,
+    5 more than the bound counts.  The 8 bytes a header without content size leaves unused hide that; a 15-byte header does not, so
+    with the bound alone a tensor of one byte — or one whose size is one more than a multiple of the block size — is refused."""
+    tensors = list(tensors)
+    if not tensors:
+        raise ValueError("compress_stream_device: no tensors")
+    return compress_stream_device_into(tensors, None, None, level, block_size_id, checksum, True)[0]
 
 
 def stream_info_device(src):
@@ -598,10 +662,11 @@ def compress_tensors_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, c
     against byte planes for activation-like bf16 (randn * 1.0) and for bf16 / fp32 weights at levels 30 and above: include/lizard_amd.h
     has the table.  planes="bits" with split=False, or another value of `planes`, raises ValueError.
     In this order: one split launch (split_planes_device) for the tensors whose element size is above 1 — none with split=False,
-    which compresses every tensor's own bytes and records element size 1 —, one batch of LizardGPU_compressFrames_device over all
-    tensors, all headers written into one host buffer and uploaded with one copy, one torch.cat.  No payload byte crosses PCIe.
-    Memory: the split bytes are a temporary of the size of the batch (beside the frames' LizardGPU_compressFrameBound regions)."""
-    import torch
+    which compresses every tensor's own bytes and records element size 1 —, all headers written into one host buffer, ONE call of
+    LizardGPU_compressStream_device over all tensors with the headers as its prefixes (compress_stream_device_into), which writes
+    every header and every frame once, to its place.  No payload byte crosses PCIe.
+    Memory: the split bytes are a temporary of the size of the batch, beside the one allocation of LizardGPU_compressStreamBound bytes
+    of which the result is a view."""
     L = _lib.lib()
     if planes not in ("bytes", "bits"):
         raise ValueError(f"compress_tensors_device: planes={planes!r} is neither 'bytes' nor 'bits'")
@@ -631,17 +696,15 @@ def compress_tensors_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, c
     elif wide:
         for i, p in zip(wide, split_planes_device([raw[i] for i in wide], [descs[i].elemSize for i in wide])):
             raw[i] = p
-    frames = _compress_frames_device(raw, level, block_size_id, checksum, True, STREAM_FRAME_SLACK)
     host = np.zeros(len(descs) * TENSOR_HEADER_MAX, dtype=np.uint8)
-    at, spans = 0, []
+    at, headers = 0, []
     for i, d in enumerate(descs):
         n = L.LizardGPU_tensorHeaderWrite2(host.ctypes.data + at, host.size - at, ctypes.byref(d))
         if not n:
             raise _lib.LizardAmdError(f"compress_tensors_device: tensor {i}: LizardGPU_tensorHeaderWrite2 refused the descriptor")
-        spans.append((at, at + n))
+        headers.append(host[at:at + n].tobytes())
         at += n
-    headers = torch.from_numpy(host[:at]).to(device)
-    return torch.cat([x for (a, b), f in zip(spans, frames) for x in (headers[a:b], f)])
+    return compress_stream_device_into(raw, None, headers, level, block_size_id, checksum, True)[0]
 
 
 def _tensor_stream_index(src, what):

@@ -22,6 +22,7 @@
 #include "unframe_walk.h"      // lz_unframe_walk_kernel: the walk over a frame in device memory (LizardGPU_decompressFrame_device)
 #include "lz_frame_pack.h"     // lz_frame_scan_kernel / lz_frame_gather_kernel: a frame assembled in device memory (LizardGPU_compressFrame_device)
 #include "lz_frames_pack.h"    // the same for a batch of frames, and their checksums (LizardGPU_compressFrames_device)
+#include "lz_stream_pack.h"    // the same for a batch of frames back to back in one buffer (LizardGPU_compressStream_device)
 #include "unframes_kernels.h"  // a batch of frames walked, decoded and settled in device memory (LizardGPU_decompressFrames_device)
 #include "unstream_kernels.h"  // the walk across the frames of a stream in device memory (LizardGPU_decompressStream_device)
 #include "planes_kernels.h"    // the bytes of a batch of buffers split into planes and joined again (LizardGPU_splitPlanes_device)
@@ -846,6 +847,32 @@ int   lzk_frames_finish_launch(const LzFramesEntry* d_frames, LzFramesResult* d_
 {
     if (!d_frames || !d_results || nFrames == 0) { snprintf(t_err, sizeof t_err, "bad argument (null pointer or no frames)"); return -LIZARDGPU_ERR_ARG; }
     lz_frames_finish_launch(d_frames, d_results, nFrames, stream);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
+int   lzk_stream_pack_launch(const void* d_base, const uint64_t* d_blkOffsets, const uint32_t* d_blkSizes, const uint32_t* d_blkFrames,
+                             const void* d_slots, size_t slot, const uint32_t* d_sizes, uint64_t* d_offsets, uint32_t nb, uint32_t firstBlock,
+                             const LzFramesEntry* d_frames, LzStreamEntry* d_entries, LzStreamState* d_state, uint64_t capacity, hipStream_t stream)
+{
+    static_assert(sizeof(LzStreamEntry) == 56 && sizeof(LzStreamState) == 16, "the tables the host file fills");
+    if (!d_base || !d_blkOffsets || !d_blkSizes || !d_blkFrames || !d_slots || !d_sizes || !d_offsets || !d_frames || !d_entries || !d_state || nb == 0) {
+        snprintf(t_err, sizeof t_err, "bad argument (null pointer or no blocks)");
+        return -LIZARDGPU_ERR_ARG;
+    }
+    lz_stream_pack_launch((const u8*)d_base, (const u64*)d_blkOffsets, d_blkSizes, d_blkFrames, (const u8*)d_slots, slot, d_sizes, (u64*)d_offsets,
+                          nb, firstBlock, d_frames, d_entries, d_state, capacity, stream);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
+int   lzk_stream_finish_launch(const LzFramesEntry* d_frames, const LzStreamEntry* d_entries, const void* d_blob, const LzStreamState* d_state,
+                               uint32_t nFrames, uint64_t fixedTotal, uint64_t capacity, LzFramesResult* d_result, uint64_t* d_offsets,
+                               hipStream_t stream)
+{
+    if (!d_frames || !d_entries || !d_blob || !d_state || !d_result || !d_offsets || nFrames == 0) {
+        snprintf(t_err, sizeof t_err, "bad argument (null pointer or no frames)");
+        return -LIZARDGPU_ERR_ARG;
+    }
+    lz_stream_finish_launch(d_frames, d_entries, (const u8*)d_blob, d_state, nFrames, fixedTotal, capacity, d_result, (u64*)d_offsets, stream);
     LZ_HIP(hipGetLastError());
     return 0;
 }

@@ -89,6 +89,7 @@ typedef struct LzCtx {
     unsigned long long devFrameCompressStats[4];   /* LizardGPU_frameCompressDeviceStats (lizard_frame_device.c); since process start */
     unsigned long long devFramesDecodeStats[4];    /* LizardGPU_framesDecodeDeviceStats (lizard_unframes_device.c); since process start */
     unsigned long long devStreamDecodeStats[4];    /* LizardGPU_streamDecodeDeviceStats (lizard_unstream_device.c); since process start */
+    unsigned long long devStreamCompressStats[4];  /* LizardGPU_streamCompressDeviceStats (lizard_stream_device.c); since process start */
     unsigned long long devPlanesStats[4];          /* LizardGPU_planesStats (lizard_planes_device.c); since process start */
     unsigned long long devBitPlanesStats[4];       /* LizardGPU_bitPlanesStats (lizard_planes_device.c); since process start */
     LzStage stage[LZ_STAGES];
@@ -175,6 +176,31 @@ int   lzk_frames_pack_launch(const void* d_base, const uint64_t* d_blkOffsets, c
 int   lzk_frames_hash_launch(LzFramesEntry* d_frames, uint32_t nFrames, hipStream_t stream);
 /* header, end mark and checksum of every live entry, and every entry's result record */
 int   lzk_frames_finish_launch(const LzFramesEntry* d_frames, LzFramesResult* d_results, uint32_t nFrames, hipStream_t stream);
+/* LizardGPU_compressStream_device (lizard_stream_device.c, lz_stream_pack.h): many frames, ONE destination.  The frames' LzFramesEntry
+ * table (every entry names d_dst, limit = dstCapacity; the hash and the gather kernel of lz_frames_pack.h work from it unchanged)
+ * has a twin with what only a stream needs.  A frame's position is `fixed` + the record bytes of all blocks in front of it, and
+ * only the device knows the second term: the scan that meets the frame's first block writes it to `before`. */
+typedef struct LzStreamEntry {
+    uint64_t fixed;                     /* prefixes and headers up to and including this frame's + end marks and checksum words of the frames before it */
+    uint64_t before;                    /* DEVICE: record bytes of the blocks in front of this frame's first block (frames with blocks only) */
+    uint64_t prefixOff, prefixBytes;    /* this frame's prefix in the blob */
+    uint32_t firstBlock, lastBlock;     /* in the list of all blocks; 0xFFFFFFFF: a frame without blocks */
+    uint32_t nextSelf, nextAfter;       /* the first frame with blocks at or behind this one / behind this one; nFrames: none, the stream's end */
+    uint32_t tailBytes, reserved;       /* end mark (+ checksum word) */
+} LzStreamEntry;
+typedef struct LzStreamState { uint64_t carry; uint32_t overflow, rawRecords; } LzStreamState;   /* carry: record bytes of the chunks scanned so far */
+/* one chunk (the arguments of lzk_frames_pack_launch; firstBlock: the chunk's place in the list of all blocks): record b goes to
+ * d_dst + d_offsets[b] = carry + record bytes of the chunk's earlier blocks + its frame's fixed bytes; the carry advances, raw
+ * records are counted, the sticky overflow flag rises when a record, or the tail behind a frame's last record, would pass `capacity`,
+ * and no record that ends behind `capacity` is written */
+int   lzk_stream_pack_launch(const void* d_base, const uint64_t* d_blkOffsets, const uint32_t* d_blkSizes, const uint32_t* d_blkFrames,
+                             const void* d_slots, size_t slot, const uint32_t* d_sizes, uint64_t* d_offsets, uint32_t nb, uint32_t firstBlock,
+                             const LzFramesEntry* d_frames, LzStreamEntry* d_entries, LzStreamState* d_state, uint64_t capacity, hipStream_t stream);
+/* behind the last gather and the hash: every frame's prefix, header, end mark and checksum word, d_offsets[0 .. nFrames] and the
+ * result record (size = fixedTotal + carry, or LZK_FRAMES_OVERFLOW, and then nothing else is written) */
+int   lzk_stream_finish_launch(const LzFramesEntry* d_frames, const LzStreamEntry* d_entries, const void* d_blob, const LzStreamState* d_state,
+                               uint32_t nFrames, uint64_t fixedTotal, uint64_t capacity, LzFramesResult* d_result, uint64_t* d_offsets,
+                               hipStream_t stream);
 /* LizardGPU_decompressFrames_device (lizard_unframes_device.c, unframes_kernels.h): the four launches over a batch of frames in device
  * memory.  walk: one wave per frame whose flags have LZU_WALK (fill = 0: no tables) or LZU_DECODE (fill = 1: frame f's records go to
  * d_offs / d_words + first_f); d_res[f] tells how frame f's walk ended.  decode: record r of frame d_recFrame[r] in place in that
