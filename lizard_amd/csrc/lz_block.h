@@ -1171,7 +1171,6 @@ LZ_DEV u32 lz_compress_block(const u8* src, u32 n, u8* dst, u32 level, void* tab
         const u32 row = (level >= 30u ? level - 21u : level) - 13u;                  // lizard_common.h:240-244, :264-268
         const bool noChain = level == 12u || level == 32u || level == 33u;           // :239, :262-263: one candidate per search
         lz_hc_begin(hc, tableMem, maxBlock, noChain ? 1u : row == 4u ? 256u : 2u << row);
-        hc.noChain = noChain;
         // AUX: the level's searchLength (4 or 5), or 6 = the kernels of the noChain levels (hash5, nochain.h:4), or 7 / 8 / 9 = the
         // kernels of levels 13 / 14 / 15 and twins (hash5, searchNum 2 / 4 / 8: lz_hcN_search)
         static_assert(AUX >= 4 && AUX <= 9, "hashChain: searchLength 4 / 5, 6 = noChain, 7 / 8 / 9 = searchNum 2 / 4 / 8");

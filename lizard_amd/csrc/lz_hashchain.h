@@ -16,9 +16,17 @@
 //     lz_hc_build), into prev[p] = distance to the previous head (0 = none inside the 64 KiB window), one
 //     u16 per block position; the searches of phase B never touch a head table.
 //     (Positions the reference never inserts — the tail after the last search — are invisible: a search at
-//     X only ever follows links that start below X.  The reference never searches below nextToUpdate —
-//     every search position exceeds the previous one, see the walk through :207-339 in DESIGN.md — and
-//     tests/test_oracle pins that on the corpus.)
+//     X only ever follows links that start below X.  The reference never searches below nextToUpdate: every
+//     search position exceeds the previous one.  A wider search at X that finds something returns a match
+//     that starts at or below X and ends at X + 4 or beyond (:146-158); the next search is 2 or 3 below that
+//     END (:212, :263), the shortening steps (:243-260, :311-338) move a match's start and keep its end, and
+//     a first search after an emit is at or behind the end of what was emitted, which is above the last search
+//     (:216-219: X = ip + ml - 2; :257-260: start2 + ml2 < ip + 8 and X <= start2 + ml2 - 4; :267-275).  The
+//     noChain loop is the same flow without the :257-260 exit (nochain.h:210): it goes on with ml2 cut to 4
+//     and the end of match 2 where it was, so its next search position is what it would have been.  DESIGN.md
+//     section 3.4 has the walk; tests/test_oracle.py::test_reference_never_searches_below_next_to_update counts
+//     the searches below nextToUpdate in the oracle over the corpus and 1 700 stitched inputs at levels 12,
+//     32, 33, 13, 15, 16 and 17: none.)
 //   * chainTable is a 2^16 ring in the reference; entries are only read inside the 65535 window where
 //     the ring has no aliasing, so a full per-position array is observably the same.  A link the reference
 //     clamps to 65535 because it is longer (":30") ends its walk one step later (":92/:172" leave the
@@ -42,7 +50,8 @@
 // hash5, nochain.h:4).  Its insert is Lizard_Insert without the chain store (same conditional head update, same MIN_OFFSET), its two
 // searches test ONE candidate — the bucket's head after inserting everything below the position, which is what prev[] records — and
 // its main loop is hashchain.h:188-369 line by line except for one exit the hashChain parser has and noChain has not
-// (hashchain.h:257-260 against nochain.h:210).  So: the chain build of the level's hashLog, searchNum 1, LzHc::noChain.
+// (hashchain.h:257-260 against nochain.h:210).  So: the chain build of the level's hashLog, searchNum 1, and the arbitration without
+// that exit — selected by the parse's template argument (lz_parse_hashchain<1>), not by a run-time flag.
 //
 // Included from lz_block.h after the shared helpers.
 #pragma once
@@ -88,7 +97,6 @@ struct LzHc {
     u32* best;          // global: the first search's result per position (see above)
     u32  searchNum;     // uniform
     bool pre;           // uniform: best[] was filled for this block
-    bool noChain;       // uniform: the noChain parser's arbitration (levels 12 / 32 / 33; searchNum is 1 then)
 };
 
 template <int SEARCHLEN, int HLOG>
@@ -112,7 +120,6 @@ LZ_DEV void lz_hc_begin(LzHc& hc, void* slotMem, u32 maxBlock, u32 searchNum)
     hc.best = (u32*)m;
     hc.searchNum = searchNum;
     hc.pre = false;
-    hc.noChain = false;
 }
 
 // Eight source bytes at each of the positions base + 64 k + lane, k = 0..7 (clamped inside the segment; unconditional).
@@ -139,6 +146,13 @@ LZ_DEV lz_u128a4 lz_hc_load_links(const LzHc& hc, u32 lo)
     return *(const lz_u128a4*)(hc.links + lo + 4u * lz_lane());
 }
 
+// LZ_HC_MARK(i): marks of the paths of lz_hc_build, counters of their own in the test emulator (tests/emul/emul_api.cpp defines the
+// macro before it includes this file; tests/hc_build_inputs.py names the marks), nothing anywhere else — the LZ_STAT indices are used up.
+// 0 the scalar replay of lz_hc_visit, 1 a step that straddles a bin border, 2 a bin left while still fresh (an empty one) with a segment to
+// come, 3 a head table stored to hc.heads, 4 one loaded from it, 5 the `more` loop of pass 3, 6 a bin behind the segment's last entry left fresh.
+#ifndef LZ_HC_MARK
+#define LZ_HC_MARK(i) ((void)0)
+#endif
 // One step of pass 2: the valid lanes (ascending positions, one bin) read the head of their bucket and become the head —
 // Lizard_Insert's ":38" — through one returning exchange; returns the lane's link (":27-31").  `arena` = the bin's table,
 // slot 2^SUBLOG is a spare for the lanes that sit out.
@@ -150,6 +164,7 @@ LZ_DEV u32 lz_hc_visit(u32* arena, bool valid, u32 hl, u32 p)
     u32 seen = old;                                              // head as my own insertion sees it
     u64 pend = lz_ballot(valid && p - old < LZ_MIN_OFFSET);
     if (pend) {                                                  // ":38" did not happen for some lane: replay its bucket in order
+        LZ_HC_MARK(0);
         while (pend) {
             const u32 hv = lz_readlane(hl, lz_ctz64(pend));
             const bool mine = valid && hl == hv;
@@ -284,9 +299,9 @@ LZ_DEV void lz_hc_build(const u8* src, u32 n, const LzHc& hc, const LzHufPool& p
                     while (from < stepEnd) {
                         while (bEnd <= from) {                       // leave bins that end here (also empty ones)
                             if (!lastSeg) {
-                                if (fresh) { uint4 none; none.x = none.y = none.z = none.w = LZ_HC_NONE;
+                                if (fresh) { LZ_HC_MARK(2); uint4 none; none.x = none.y = none.z = none.w = LZ_HC_NONE;
                                              if (firstSeg) for (u32 i = lane * 4u; i < kSub; i += 256u) *(uint4*)(hc.heads + b * kSub + i) = none; }
-                                else { lz_lds_sync(); for (u32 i = lane * 4u; i < kSub; i += 256u) *(uint4*)(hc.heads + b * kSub + i) = *(const uint4*)(arena + i); }
+                                else { LZ_HC_MARK(3); lz_lds_sync(); for (u32 i = lane * 4u; i < kSub; i += 256u) *(uint4*)(hc.heads + b * kSub + i) = *(const uint4*)(arena + i); }
                             }
                             b++; bEnd = lz_readlane(myEnd, b & 63u); fresh = true;
                         }
@@ -294,11 +309,12 @@ LZ_DEV void lz_hc_build(const u8* src, u32 n, const LzHc& hc, const LzHufPool& p
                             lz_lds_sync();                           // the previous table's reads are done
                             if (firstSeg) { uint4 none; none.x = none.y = none.z = none.w = LZ_HC_NONE;
                                             for (u32 i = lane * 4u; i < kSub; i += 256u) *(uint4*)(arena + i) = none; }
-                            else for (u32 i = lane * 4u; i < kSub; i += 256u) *(uint4*)(arena + i) = *(const uint4*)(hc.heads + b * kSub + i);
+                            else { LZ_HC_MARK(4); for (u32 i = lane * 4u; i < kSub; i += 256u) *(uint4*)(arena + i) = *(const uint4*)(hc.heads + b * kSub + i); }
                             lz_lds_sync();
                             fresh = false;
                         }
                         const u32 to = bEnd < stepEnd ? bEnd : stepEnd;
+                        if (to < stepEnd) LZ_HC_MARK(1);               // the step straddles a bin border
                         const bool valid = idx >= from && idx < to;
                         const u32 l = lz_hc_visit<kSubLog>(arena, valid, hl, p);
                         if (valid) link = l;
@@ -310,9 +326,9 @@ LZ_DEV void lz_hc_build(const u8* src, u32 n, const LzHc& hc, const LzHufPool& p
             }
             if (!lastSeg) {                                          // the bins from the current one on
                 for (;;) {
-                    if (fresh) { uint4 none; none.x = none.y = none.z = none.w = LZ_HC_NONE;
+                    if (fresh) { LZ_HC_MARK(6); uint4 none; none.x = none.y = none.z = none.w = LZ_HC_NONE;
                                  if (firstSeg) for (u32 i = lane * 4u; i < kSub; i += 256u) *(uint4*)(hc.heads + b * kSub + i) = none; }
-                    else { lz_lds_sync(); for (u32 i = lane * 4u; i < kSub; i += 256u) *(uint4*)(hc.heads + b * kSub + i) = *(const uint4*)(arena + i); }
+                    else { LZ_HC_MARK(3); lz_lds_sync(); for (u32 i = lane * 4u; i < kSub; i += 256u) *(uint4*)(hc.heads + b * kSub + i) = *(const uint4*)(arena + i); }
                     if (++b >= 64u) break;
                     fresh = true;
                 }
@@ -347,6 +363,7 @@ LZ_DEV void lz_hc_build(const u8* src, u32 n, const LzHc& hc, const LzHufPool& p
                 if (hi - lo > 256u) more |= 1ull << b;               // a bin with more than 256 entries in the window: below
             }
             while (more) {                                           // skewed data only
+                LZ_HC_MARK(5);
                 const u32 b = lz_ctz64(more); more &= more - 1ull;
                 const u32 lo = lz_readlane(wLo, b), hi = lz_readlane(wHi, b);
                 for (u32 i = lo + 256u; i < hi; i += 256u) {

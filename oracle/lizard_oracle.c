@@ -350,6 +350,11 @@ static void parse_pricefast(lzo_ctx* c, uint32_t S, uint32_t E)
 /* ---- hashChain parser: reference lib/lizard_parser_hashchain.h ------------------------------------ */
 #define HC_OPTIMAL_ML 18        /* (ML_MASK_LZ4-1)+MINMATCH, hashchain.h:3 */
 
+/* Searches that arrived below nextToUpdate (their insert does nothing and moves nextToUpdate BACK): the chain build of
+ * lizard_amd/csrc/lz_hashchain.h assumes there are none; tests/test_oracle.py reads this through lzo_searches_below_next_to_update(). */
+static unsigned long long g_below_ntu;
+#define NOTE_SEARCH(c, ip) do { if ((ip) < (c)->nextToUpdate) __atomic_fetch_add(&g_below_ntu, 1ull, __ATOMIC_RELAXED); } while (0)
+
 static uint32_t hc_hash(const lzo_ctx* c, uint32_t pos)
 {
     return c->prm.searchLength == 4 ? hash4(c->src + pos, c->prm.hashLog) : hash5(c->src + pos, c->prm.hashLog);
@@ -380,6 +385,7 @@ static int hc_find_best(lzo_ctx* c, uint32_t ip, uint32_t iLimit, uint32_t* ref)
     const uint32_t lowLimit = (LZO_DICT_SIZE + maxDist >= cur) ? LZO_DICT_SIZE : cur - maxDist;
     int attempts = (int)c->prm.searchNum;
     uint32_t ml = 0, mi;
+    NOTE_SEARCH(c, ip);
     hc_insert(c, ip);
     mi = c->table[hc_hash(c, ip)];
     while (mi < cur && mi >= lowLimit && attempts) {
@@ -407,6 +413,7 @@ static int hc_wider(lzo_ctx* c, uint32_t ip, uint32_t iLow, uint32_t iHigh, int 
     const int LLdelta = (int)(ip - iLow);
     int attempts = (int)c->prm.searchNum;
     uint32_t mi;
+    NOTE_SEARCH(c, ip);
     hc_insert(c, ip);
     mi = c->table[hc_hash(c, ip)];
     while (mi < cur && mi >= lowLimit && attempts) {
@@ -448,6 +455,7 @@ static int nc_find_best(lzo_ctx* c, uint32_t ip, uint32_t iLimit, uint32_t* ref)
     const uint32_t maxDist = (1u << c->prm.windowLog) - 1, cur = ip + LZO_DICT_SIZE;
     const uint32_t lowLimit = (LZO_DICT_SIZE + maxDist >= cur) ? LZO_DICT_SIZE : cur - maxDist;
     uint32_t ml = 0, mi;
+    NOTE_SEARCH(c, ip);
     nc_insert(c, ip);
     mi = c->table[hash5(src + ip, c->prm.hashLog)];
     if (mi < cur && mi >= lowLimit) {
@@ -468,6 +476,7 @@ static int nc_wider(lzo_ctx* c, uint32_t ip, uint32_t iLow, uint32_t iHigh, int 
     const uint32_t lowLimit = (LZO_DICT_SIZE + maxDist >= cur) ? LZO_DICT_SIZE : cur - maxDist;
     const int LLdelta = (int)(ip - iLow);
     uint32_t mi;
+    NOTE_SEARCH(c, ip);
     nc_insert(c, ip);
     mi = c->table[hash5(src + ip, c->prm.hashLog)];
     if (mi < cur && mi >= lowLimit) {
@@ -586,6 +595,84 @@ static void parse_hashchain(lzo_ctx* c, uint32_t S, uint32_t E)
         goto search3;
     }
     emit_last_literals(c, (uint32_t)anchor, E);
+}
+
+/* ---- test-only exports: the match finder's state as a function of the block's bytes ----------------------------------- */
+
+unsigned long long lzo_searches_below_next_to_update(int reset)
+{
+    return reset ? __atomic_exchange_n(&g_below_ntu, 0ull, __ATOMIC_RELAXED) : __atomic_load_n(&g_below_ntu, __ATOMIC_RELAXED);
+}
+
+/* The sequential model of lizard_amd/csrc/lz_hashchain.h's tables (contract: lizard_oracle.h).  One context, the inserts and first
+ * searches above at ascending positions: Lizard_Insert / Lizard_InsertNoChain reaches p with everything below p inserted, the head
+ * it finds there is what it records for p, and Lizard_InsertAndFindBestMatch(NoChain) at p walks from that same head. */
+#define HC_MODEL_CAP 17u
+int lzo_hc_tables(const void* srcv, int n, int level, uint16_t* prev, uint32_t* two, uint8_t* hit, uint32_t* first, uint8_t* mayBeOpen)
+{
+    lzo_ctx c;
+    const uint8_t* src = (const uint8_t*)srcv;
+    uint32_t p, nIns;
+    int nochain;
+    if (!lzo_get_params(level, &c.prm) || (c.prm.parser != P_HASHCHAIN && c.prm.parser != P_NOCHAIN)) return -1;
+    if (n < 0 || (unsigned)n > (unsigned)LZO_MAX_INPUT) return -1;
+    nochain = c.prm.parser == P_NOCHAIN;
+    nIns = n >= 8 ? (uint32_t)n - 7u : 0u;
+    c.src = src;
+    c.table = (uint32_t*)calloc((size_t)1 << c.prm.hashLog, sizeof(uint32_t));
+    c.chain = (uint32_t*)calloc((size_t)1 << 16, sizeof(uint32_t));
+    c.nextToUpdate = 0;
+    if (!c.table || !c.chain) { free(c.table); free(c.chain); return -1; }
+    for (p = 0; p < nIns; p++) {
+        const uint32_t S0 = p & ~((uint32_t)LZO_SUBBLOCK - 1u);
+        const uint32_t E = S0 + LZO_SUBBLOCK < (uint32_t)n ? S0 + LZO_SUBBLOCK : (uint32_t)n;     /* the sub-block the parse is in at p */
+        const int mflimit = (int)E - (int)LZO_MFLIMIT;
+        const uint32_t matchlimit = E - LZO_LASTLITERALS;
+        const int searched = (int)p < mflimit;                     /* hashchain.h:204 / nochain.h:162: the parse searches below mflimit only */
+        uint32_t head, d, ref = 0;
+        int ml;
+        if (nochain) nc_insert(&c, p); else hc_insert(&c, p);      /* everything below p is in; p is not */
+        head = c.table[nochain ? hash5(src + p, c.prm.hashLog) : hc_hash(&c, p)];
+        d = head ? p + LZO_DICT_SIZE - head : 0u;                  /* 0 = the bucket is empty (LIZARD_RESET_MEM state) */
+        prev[p] = (uint16_t)(d <= 65535u ? d : 0u);
+        /* where the parse never searches, any limit that leaves 4 bytes answers "does it find anything" (p + 8 <= n).  Where it
+         * does, the limit is the parse's cut to p + HC_MODEL_CAP: every length up to 16 and the choice among such candidates are what
+         * they are under the parse's own limit, and a length of 17 says "more than 16" (checked against mayBeOpen below).  Without
+         * the cut a run of n bytes costs n * searchNum * n / 2 byte compares here. */
+        ml = find_best(&c, p, !searched ? p + LZO_MINMATCH : matchlimit < p + HC_MODEL_CAP ? matchlimit : p + HC_MODEL_CAP, &ref);
+        hit[p] = (uint8_t)(ml > 0);
+        if (first) first[p] = (searched && ml) ? (uint32_t)ml | ((p - ref) << 16) : 0u;
+    }
+    for (p = 0; p < nIns; p++) {
+        const uint32_t d1 = prev[p], d2 = d1 ? prev[p - d1] : 0u;
+        two[p] = d1 | ((d1 && d2 && d1 + d2 <= 65535u) ? (d1 + d2) << 16 : 0u);
+    }
+    if (mayBeOpen) {
+        /* lz_hc_hits may leave the first search to the parse (a) when one of the first four in-window candidates agrees with p in
+         * every byte the pass compares (16, or 8 when p + 16 > n) and the match may be longer than that, (b) when the chain has a
+         * fifth in-window candidate within searchNum.  The candidates: the links recorded above. */
+        for (p = 0; p < nIns; p++) {
+            const uint32_t S0 = p & ~((uint32_t)LZO_SUBBLOCK - 1u);
+            const uint32_t E = S0 + LZO_SUBBLOCK < (uint32_t)n ? S0 + LZO_SUBBLOCK : (uint32_t)n;
+            const uint32_t room = (int)p < (int)E - (int)LZO_MFLIMIT ? E - LZO_LASTLITERALS - p : 0u;
+            const uint32_t seen = p + 16u <= (uint32_t)n ? 16u : 8u;
+            uint32_t m = p, a;
+            uint8_t open = 0;
+            for (a = 0; a < c.prm.searchNum && !open; a++) {
+                const uint32_t dd = prev[m];
+                if (!dd || p - (m - dd) > 65535u) break;
+                m -= dd;
+                if (a >= 4u) open = 1;
+                else if (p - m >= LZO_MIN_OFFSET && room > seen && !memcmp(src + p, src + m, seen)) open = 1;
+            }
+            mayBeOpen[p] = open;
+            /* a first search that finds more than 16 bytes is one the kernel may leave open: the candidate is among the first
+             * four (a) or behind them (b).  The cut of the limit above rests on this. */
+            if (first && (first[p] & 0xFFFFu) > 16u && !open) { free(c.table); free(c.chain); return -2; }
+        }
+    }
+    free(c.table); free(c.chain);
+    return (int)nIns;
 }
 
 /* ---- sub-block container: reference lib/lizard_compress.c:141-250 ------------------------------- */

@@ -41,6 +41,29 @@ int lzo_compress(const void* src, void* dst, int srcSize, int dstCapacity, int l
  * "store raw". */
 size_t lzo_huf_compress(void* dst, size_t dstCapacity, const void* src, size_t srcSize);
 
+/* Test-only: the state of the hashChain / noChain match finder (levels 12-17, 32-38) as a function of the block's bytes, from
+ * this file's restatements of Lizard_Insert(NoChain) and Lizard_InsertAndFindBestMatch(NoChain) driven on ONE context at ascending
+ * positions p = 0 .. nIns - 1, nIns = n >= 8 ? n - 7 : 0 — the sequential model the chain build of the product's kernels
+ * (lz_hc_build, lz_hc_hits_plain, lz_hc_hits) is compared with.  Per position:
+ *   prev[p]      distance from p to the head of p's bucket at the moment the insert reaches p; 0 = empty bucket or farther than
+ *                65535 (exactly 65535 stays); the head moves only when p - head >= MIN_OFFSET (hashchain.h:38, nochain.h:20)
+ *   two[p]       prev[p] | s << 16, s = prev[p] + prev[p - prev[p]] when both links exist and the sum is <= 65535, else 0
+ *   hit[p]       1 when the first search at p returns a length above 0
+ *   first[p]     (may be NULL) length | offset << 16 of that search under the limit the parse passes at p (the end of p's 128 KiB
+ *                sub-block or of the block, minus LASTLITERALS); 0 = nothing found, or the parse never searches at p (p at or
+ *                beyond the sub-block's mflimit).  Exact where the length is at most 16; a longer match is reported with length 17
+ *                (the model cuts the limit to p + 17: a run would cost n^2 * searchNum compares otherwise), and mayBeOpen[p] is 1
+ *                at every such position (checked: -2 is returned if not)
+ *   mayBeOpen[p] (may be NULL) 1 when lz_hc_hits may leave the first search at p to the parse: one of the first four in-window
+ *                chain candidates agrees with p in all the bytes that pass compares (16, or 8 when p + 16 > n) and the limit
+ *                leaves room for more, or the chain has a fifth in-window candidate within searchNum
+ * Returns nIns, -1 for a level without these parsers (first / mayBeOpen are filled together or not at all). */
+int lzo_hc_tables(const void* src, int n, int level, uint16_t* prev, uint32_t* two, uint8_t* hit, uint32_t* first, uint8_t* mayBeOpen);
+
+/* Test-only: number of searches (both kinds, hashChain and noChain) since the last reset that arrived at a position below
+ * nextToUpdate; reset != 0 clears the counter. */
+unsigned long long lzo_searches_below_next_to_update(int reset);
+
 /* RDG_genBuffer (reference programs/datagen.c:153): deterministic synthetic data. */
 void lzo_datagen(void* buffer, size_t size, double matchProba, double litProba, unsigned seed);
 

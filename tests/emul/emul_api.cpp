@@ -1,6 +1,9 @@
 // tests/emul/emul_api.cpp — TEST INFRASTRUCTURE ONLY: C entry points that run the product's kernel
 // bodies (lizard_amd/csrc/lz_block.h, ...) on the CPU SIMT emulator. Loaded by tests via ctypes.
 #include "lz_wave.h"            // tests/emul/lz_wave.h (emulator) — must come first, see the shared guard
+// marks of lz_hc_build's paths (lz_hashchain.h LZ_HC_MARK): counters of their own, read with emul_hc_marks()
+extern "C" unsigned long long lzemu_hc_marks[16];
+#define LZ_HC_MARK(i) do { if (lz_lane() == 0) __atomic_add_fetch(&lzemu_hc_marks[i], 1ull, __ATOMIC_RELAXED); } while (0)
 #include "../../lizard_amd/csrc/lz_block.h"
 #include "../../lizard_amd/csrc/lz_unpack.h"
 #include "../../lizard_amd/csrc/lz_split.h"
@@ -24,10 +27,71 @@ void entry_block(void* a)
 
 
 unsigned long long lzemu_stats[64];
+unsigned long long lzemu_hc_marks[16];
 // event counters of the kernels' LZ_STAT marks since the last reset
 extern "C" void emul_stats(unsigned long long* out, int reset)
 {
     for (int i = 0; i < 64; i++) { out[i] = __atomic_load_n(&lzemu_stats[i], __ATOMIC_RELAXED); if (reset) __atomic_store_n(&lzemu_stats[i], 0ull, __ATOMIC_RELAXED); }
+}
+
+// the marks of lz_hc_build since the last reset, `count` (<= 16) of them
+extern "C" void emul_hc_marks(unsigned long long* out, int count, int reset)
+{
+    for (int i = 0; i < count && i < 16; i++) {
+        out[i] = __atomic_load_n(&lzemu_hc_marks[i], __ATOMIC_RELAXED);
+        if (reset) __atomic_store_n(&lzemu_hc_marks[i], 0ull, __ATOMIC_RELAXED);
+    }
+}
+
+// What lz_compress_block does in front of the hashChain / noChain parse, and nothing else: lz_hc_begin, lz_hc_build<searchLen, hashLog>
+// and lz_hc_hits (pre != 0: levels 16 / 17 / 37 / 38) or lz_hc_hits_plain, on a slot of exactly the size the library gives a wave
+// for blocks of n bytes (lizard_gpu.hip ensure_hc_slots: LZ_HC_SLOT_BYTES of n rounded up to 64 KiB, without best[] when pre == 0)
+// filled with 0xB7 between 64 canary bytes, and a chain-build region filled with 0x3C3C3C3C.  Copies out prev / chain2 / best for
+// p < nIns = n - 7 and the (nIns + 63) / 64 words of hits.  Returns 0, 1 = a canary changed, -1 = no such form.
+namespace {
+struct HcArgs { const u8* src; u32 n; u32 searchNum; u32 pre; void* slot; u32 maxBlock; u32* region; u32 poolMask; LzHc hc; };
+template <int SEARCHLEN, int HLOG>
+void entry_hc_tables(void* a)
+{
+    HcArgs* x = (HcArgs*)a;
+    LzHufPool pool; pool.base = x->region; pool.mask = &x->poolMask; pool.count = 1; pool.stride = LZ_HC_REGION_WORDS;
+    LzStreams st;
+    LzHc hc;
+    lz_hc_begin(hc, x->slot, x->maxBlock, x->searchNum);
+    lz_hc_build<SEARCHLEN, HLOG>(x->src, x->n, hc, pool, st);
+    hc.pre = x->pre != 0u;
+    if (x->pre) lz_hc_hits(x->src, x->n, hc); else lz_hc_hits_plain(x->src, x->n, hc);
+    if (lz_lane() == 0) x->hc = hc;
+}
+}  // namespace
+
+extern "C" int emul_hc_tables(const void* src, int n, int searchLen, int hashLog, int searchNum, int pre,
+                              unsigned short* prev, unsigned* chain2, unsigned long long* hits, unsigned* best, unsigned seed)
+{
+    const size_t kGuard = 64;
+    const size_t cap = (((size_t)(n > 0 ? n : 1)) + 65535u) & ~(size_t)65535u;
+    const size_t slotBytes = LZ_HC_SLOT_BYTES(cap) - (pre ? 0u : 4u * cap);
+    void (*fn)(void*) = searchLen == 5 && hashLog == 18 ? entry_hc_tables<5, 18> : searchLen == 4 && hashLog == 18 ? entry_hc_tables<4, 18>
+                      : searchLen == 5 && hashLog == 14 ? entry_hc_tables<5, 14> : nullptr;
+    if (!fn || n < 0) return -1;
+    u8* mem = nullptr;
+    if (posix_memalign((void**)&mem, 64, slotBytes + 2 * kGuard)) abort();
+    memset(mem, 0xC3, kGuard); memset(mem + kGuard, 0xB7, slotBytes); memset(mem + kGuard + slotBytes, 0xC3, kGuard);
+    HcArgs a;
+    a.src = (const u8*)src; a.n = (u32)n; a.searchNum = (u32)searchNum; a.pre = (u32)pre; a.slot = mem + kGuard; a.maxBlock = (u32)(n > 0 ? n : 1);
+    a.poolMask = 0;
+    a.region = (u32*)aligned_alloc(64, (4 * LZ_HC_REGION_WORDS + 63) & ~(size_t)63);
+    memset(a.region, 0x3C, 4 * LZ_HC_REGION_WORDS);
+    lzemu::run_wave(fn, &a, seed);
+    const size_t nIns = n >= 8 ? (size_t)n - 7u : 0u;
+    memcpy(prev, a.hc.prev, 2 * nIns);
+    memcpy(chain2, a.hc.chain2, 4 * nIns);
+    memcpy(hits, a.hc.hits, 8 * ((nIns + 63) / 64));
+    if (pre) memcpy(best, a.hc.best, 4 * nIns);
+    int bad = a.poolMask != 0u;                                // the region went back
+    for (size_t i = 0; i < kGuard; i++) bad |= mem[i] != 0xC3 || mem[kGuard + slotBytes + i] != 0xC3;
+    free(mem); free(a.region);
+    return bad;
 }
 
 #ifndef LZ_EMUL_EXACT_AREAS

@@ -100,3 +100,71 @@ def test_oracle_known_answers_p50_64m(key):
         h = xxhash.xxh64(out.raw[:n], seed=h).intdigest()
     assert tot == GOLDEN["p50_64m"][key]["sum"]
     assert "%016x" % h == GOLDEN["p50_64m"][key]["xxh64_chain"]
+
+
+# ---- the sequential model of the hashChain tables (lzo_hc_tables) and the property the chain build rests on ----
+
+def _plain_hc_tables(data, hash_len, hash_log, search_num):
+    """prev / two / hit as oracle/lizard_oracle.h defines them, from a dictionary of bucket heads and nothing else."""
+    n_ins = len(data) - 7 if len(data) >= 8 else 0
+    heads, prev = {}, []
+    for p in range(n_ins):
+        if hash_len == 4:
+            h = ((int.from_bytes(data[p:p + 4], "little") * 2654435761) & 0xFFFFFFFF) >> (32 - hash_log)
+        else:
+            h = (((int.from_bytes(data[p:p + 8], "little") * 889523592379) << 24) & 0xFFFFFFFFFFFFFFFF) >> (64 - hash_log)
+        head = heads.get(h)
+        prev.append(p - head if head is not None and p - head <= 65535 else 0)
+        if head is None or p - head >= 8:
+            heads[h] = p
+    two, hit = [], []
+    for p in range(n_ins):
+        d1 = prev[p]
+        d2 = prev[p - d1] if d1 else 0
+        two.append(d1 | ((d1 + d2) << 16 if d1 and d2 and d1 + d2 <= 65535 else 0))
+        m, found = p, 0
+        for _ in range(search_num):
+            if not prev[m] or p - (m - prev[m]) > 65535:
+                break
+            m -= prev[m]
+            if p - m >= 8 and data[m:m + 4] == data[p:p + 4]:
+                found = 1
+                break
+        hit.append(found)
+    return prev, two, hit
+
+
+@pytest.mark.parametrize("level,hash_len,search_num", [(12, 5, 1), (13, 5, 2), (16, 4, 16)])
+def test_hc_tables_model_against_plain_python(level, hash_len, search_num):
+    """Both hash lengths and the noChain insert, on data with links on both sides of MIN_OFFSET."""
+    for name, data in (("p50", util.datagen(2000, 0.5, 0.0, 1)), ("zeros", bytes(300)), ("abc", b"abc" * 200)):
+        got = util.oracle_hc_tables(data, level)
+        prev, two, hit = _plain_hc_tables(data, hash_len, 18, search_num)
+        assert got["prev"] == prev, (name, level)
+        assert got["two"] == two, (name, level)
+        assert got["hit"] == hit, (name, level)
+        assert any(hit) and not all(hit), (name, level)
+
+
+N_RANDOM, N_LONG = 1500, 200
+
+
+def test_reference_never_searches_below_next_to_update():
+    """lz_hashchain.h builds the chain ahead of the parse: a search at X sees every position below X inserted, once.  That is the
+    reference's behaviour only while no search arrives below nextToUpdate (such a search inserts nothing, moves nextToUpdate BACK,
+    and the positions in between are inserted a second time by the next search).  The oracle counts such searches."""
+    import random
+    from test_random_parity import make_case, make_long_case
+    O = util.oracle()
+    levels = (12, 32, 33, 13, 15, 16, 17)
+    O.lzo_searches_below_next_to_update(1)
+    inputs = [d for _, d in util.corpus(small=True)]
+    inputs += [d for _, d in list(CORPUS_LONG.items())[::3] if len(d) <= (1 << 20)]
+    rng = random.Random(20260219)
+    inputs += [make_case(rng, 70000) for _ in range(N_RANDOM)]
+    inputs += [make_long_case(rng, 300000) for _ in range(N_LONG)]
+    for i, data in enumerate(inputs):
+        for level in levels:
+            util.compress_with(O.lzo_compress, data, level)
+            assert O.lzo_searches_below_next_to_update(1) == 0, (i, len(data), level)
+

@@ -39,8 +39,26 @@ def oracle():
         L.lzo_level_supported.argtypes = [_c.c_int]
         L.lzo_datagen.argtypes = [_c.c_void_p, _c.c_size_t, _c.c_double, _c.c_double, _c.c_uint]
         L.lzo_huf_compress.argtypes = [_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t]; L.lzo_huf_compress.restype = _c.c_size_t
+        L.lzo_hc_tables.argtypes = [_c.c_void_p, _c.c_int, _c.c_int] + [_c.c_void_p] * 5; L.lzo_hc_tables.restype = _c.c_int
+        L.lzo_searches_below_next_to_update.argtypes = [_c.c_int]; L.lzo_searches_below_next_to_update.restype = _c.c_ulonglong
         _oracle = L
     return _oracle
+
+
+def oracle_hc_tables(data, level, with_first=False):
+    """lzo_hc_tables (oracle/lizard_oracle.h): the sequential model of the hashChain tables -> dict of lists, nIns entries each."""
+    n = len(data)
+    n_ins = n - 7 if n >= 8 else 0
+    src = ctypes.create_string_buffer(bytes(data), n) if n else ctypes.create_string_buffer(1)
+    prev, two, hit = (_c.c_uint16 * max(n_ins, 1))(), (_c.c_uint32 * max(n_ins, 1))(), (_c.c_uint8 * max(n_ins, 1))()
+    first = (_c.c_uint32 * max(n_ins, 1))() if with_first else None
+    may = (_c.c_uint8 * max(n_ins, 1))() if with_first else None
+    r = oracle().lzo_hc_tables(src, n, level, prev, two, hit, first, may)
+    assert r == n_ins, (r, n_ins, level)
+    out = {"prev": prev[:n_ins], "two": two[:n_ins], "hit": hit[:n_ins]}
+    if with_first:
+        out["first"], out["mayBeOpen"] = first[:n_ins], may[:n_ins]
+    return out
 
 
 _ref = None
