@@ -19,7 +19,9 @@
  *            LizardGPU_decompressFrames_device, LizardGPU_decompressStream_device ...)
  *   Part 3c  tensor streams: element bytes split into planes before compressing (LizardGPU_splitPlanes_device,
  *            LizardGPU_joinPlanes_device) or, opt-in, element bits (LizardGPU_splitBitPlanes_device, LizardGPU_joinBitPlanes_device),
- *            and the tensor header, a skippable frame (LizardGPU_tensorHeaderWrite / Read, with a filter: Write2 / Read2)
+ *            either of them after an XOR with an earlier version of the buffer, opt-in and per buffer
+ *            (LizardGPU_splitPlanesXor_device, LizardGPU_joinPlanesXor_device), and the tensor header, a skippable frame
+ *            (LizardGPU_tensorHeaderWrite / Read, with a filter: Write2 / Read2, with a base: Write3 / Read3)
  *
  * Plain C, plain pointers and sizes; no HIP or torch types in any signature (a HIP stream is passed
  * as an opaque void*).
@@ -789,6 +791,67 @@ typedef struct { uint32_t elemSize; uint32_t ndim; uint64_t nbytes; uint64_t sha
                  uint32_t filter; uint32_t reserved; } LizardGPU_tensorDesc2_t;
 size_t LizardGPU_tensorHeaderWrite2(void* dst, size_t dstCapacity, const LizardGPU_tensorDesc2_t* desc); /* bytes, or 0 */
 int    LizardGPU_tensorHeaderRead2(const void* src, size_t srcSize, LizardGPU_tensorDesc2_t* desc, size_t* headerBytes);
+
+/* XOR with a base: the third filter, OPT-IN and per buffer, in front of either plane filter.  Callers rarely hold a tensor alone:
+ * a checkpoint lies beside the previous one, a fine-tune beside its base model, a cache page beside its earlier version, and the
+ * reader will hold that earlier version too.  XOR against it turns every unchanged bit into a zero, and the plane filters put those
+ * zeros into runs.  For a buffer of `size` bytes with base b (`size` INTERLEAVED bytes, the earlier version as it lies in memory):
+ *     split   dst = split(src XOR b)          join   dst = join(src) XOR b
+ * where split / join are exactly the byte-plane or bit-plane layouts above; every byte takes part — whole elements, the ragged end
+ * of the planes and the bytes behind the last whole element.  The XOR happens in registers (planes_kernels.h, bitplanes_kernels.h):
+ * 3 bytes of memory traffic per payload byte where XOR-then-split through a temporary moves 5, and no third buffer.
+ * Stream / raw, reference library, 128 KiB blocks, w = randn(2^19) * 0.02, the tensor w + step with |step| <= lr (an Adam-sized
+ * update), the base w (profiles/xor_base_ratio.json; "bytes" / "bits" = the filter alone):
+ *                                   level 10                            level 30
+ *                                   bytes   XOR+bytes  bits    XOR+bits   bytes   XOR+bytes  bits    XOR+bits
+ *     bf16, lr 1e-5 (14 % differ)   0.8430  0.3090     0.7638  0.3241     0.7455  0.1457     0.7501  0.1660
+ *     fp16, lr 1e-5 (55 % differ)   1.0000  0.4935     0.9375  0.5074     1.0000  0.2793     0.9375  0.3323
+ *     fp32, lr 1e-5 (all differ)    0.9215  0.6608     0.8818  0.6644     0.8728  0.5735     0.8751  0.5832
+ *     bf16, lr 1e-4 (61 % differ)   0.8433  0.5180     0.7651  0.4783     0.7455  0.2897     0.7504  0.3477
+ *     bf16, lr 1e-3 (96 % differ)   0.8431  0.6546     0.7632  0.6307     0.7454  0.5811     0.7500  0.5403
+ *     bf16, 1 % replaced            0.8435  0.3753     0.7651  0.2122     0.7456  0.0751     0.7505  0.0890
+ *     bf16, UNRELATED base          0.8431  0.9130     0.7645  0.7652     0.7456  0.7489     0.7504  0.7645
+ * USE IT ONLY AGAINST A BASE THE DATA DERIVES FROM.  With an unrelated base it LOSES at level 10 with byte planes (0.9130 against
+ * 0.8431) and roughly ties elsewhere; nothing chooses for the caller.  With a base, byte and bit planes are close; bytes are ahead
+ * at level 30 for small updates.
+ *
+ * LizardGPU_splitPlanesXor_device / LizardGPU_joinPlanesXor_device: the whole contract of LizardGPU_splitPlanes_device /
+ * LizardGPU_splitBitPlanes_device, `filter` (LIZARDGPU_FILTER_BYTE_PLANES / LIZARDGPU_FILTER_BIT_PLANES) choosing the layout — HOST
+ * arrays of device pointers of any alignment (the bases too), ONE launch, SYNCHRONOUS and ordered after what `stream` holds, entries
+ * of size 0 skipped (their pointers may be NULL), -LIZARDGPU_ERR_ARG with NOTHING launched for a null d_dsts / d_srcs / sizes /
+ * elemSizes, an elemSizes[i] outside {1, 2, 4, 8}, a null src or dst in an entry of non-zero size, a batch of 2^32 tiles or more —
+ * and for a `filter` that is neither value (judged first, for nBuffers == 0 as well); else nBuffers == 0 returns 0.
+ * d_bases[i] == NULL: buffer i has no base; d_bases == NULL: none has; such a buffer's result is byte for byte the plain filter's,
+ * in the same launch (a wave-uniform branch per tile).  Nothing outside d_bases[i][0 .. sizes[i]) is read.  A dst that overlaps a
+ * src or a base is the caller's error; a base may be its buffer's src (the split is then all zeros).
+ * LizardGPU_planesXorStats: these entries' own counters — [0] buffers split, [1] buffers joined, [2] payload bytes, [3] launches;
+ * LizardGPU_planesStats / LizardGPU_bitPlanesStats keep counting the plain entries alone. */
+int LizardGPU_splitPlanesXor_device(size_t nBuffers, void* const* d_dsts, const void* const* d_srcs, const void* const* d_bases,
+                                    const size_t* sizes, const uint32_t* elemSizes, unsigned filter, void* stream);
+int LizardGPU_joinPlanesXor_device (size_t nBuffers, void* const* d_dsts, const void* const* d_srcs, const void* const* d_bases,
+                                    const size_t* sizes, const uint32_t* elemSizes, unsigned filter, void* stream);
+int LizardGPU_planesXorStats(unsigned long long out[4]);
+
+/* The tensor header of a tensor that was XORed with a base: tag "LZT3".  LizardGPU_tensorHeaderWrite / Read / Write2 / Read2 stay
+ * byte for byte what they are and go on refusing "LZT3": a reader that cannot apply a base must not hand out the XORed bytes.
+ * LizardGPU_tensorDesc3_t: the v2 fields with `reserved` named `flags`, then baseTag — an opaque number of the caller's (a step
+ * number, a hash of their own) that the writer stores and a reader compares: it is how a reader learns that it was handed the wrong
+ * base.  The library does not hash bases.  "LZT3" bytes: the "LZT2" layout with
+ *   payload 6         the filter, 0 or 1
+ *           7         the flags: LIZARDGPU_TENSOR_XOR_BASE (1)
+ *          40 .. 47   LE64 baseTag
+ *          48 ..      ndim x LE64 dims            payload length 48 + 8 * ndim
+ * Write3: flags == 0 writes exactly Write2's bytes ("LZT1" / "LZT2") and refuses a non-zero baseTag; flags == 1 writes "LZT3"; any
+ * other flags, and everything Write2 refuses, write nothing and return 0.  One encoding per meaning.
+ * Read3: accepts all three tags; flags and baseTag come back as 0 for "LZT1" / "LZT2"; "LZT3" with byte 7 != 1 or byte 6 > 1 is
+ * -LIZARDGPU_FRAME_ERR_frameType_unknown.  Every field is judged as soon as the bytes in hand hold it, so a prefix of a valid header
+ * is -LIZARDGPU_FRAME_ERR_frameHeader_incomplete, never unknown: with fewer than 12 bytes a length is accepted when it is valid for
+ * any of the three tags; once the tag is in hand the length and ndim must agree with that tag's fixed part (40 or 48). */
+#define LIZARDGPU_TENSOR_XOR_BASE 1u
+typedef struct { uint32_t elemSize; uint32_t ndim; uint64_t nbytes; uint64_t shape[8]; char dtype[24];
+                 uint32_t filter; uint32_t flags; uint64_t baseTag; } LizardGPU_tensorDesc3_t;
+size_t LizardGPU_tensorHeaderWrite3(void* dst, size_t dstCapacity, const LizardGPU_tensorDesc3_t* desc); /* bytes, or 0 */
+int    LizardGPU_tensorHeaderRead3(const void* src, size_t srcSize, LizardGPU_tensorDesc3_t* desc, size_t* headerBytes);
 
 #ifdef __cplusplus
 }

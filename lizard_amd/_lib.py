@@ -132,6 +132,12 @@ def lib():
     L.LizardGPU_tensorHeaderRead2.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]; L.LizardGPU_tensorHeaderRead2.restype = c.c_int
     L.LizardGPU_tensorHeaderWrite.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p]; L.LizardGPU_tensorHeaderWrite.restype = c.c_size_t
     L.LizardGPU_tensorHeaderRead.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]; L.LizardGPU_tensorHeaderRead.restype = c.c_int
+    for name in ("LizardGPU_splitPlanesXor_device", "LizardGPU_joinPlanesXor_device"):
+        getattr(L, name).argtypes = [c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint, c.c_void_p]
+        getattr(L, name).restype = c.c_int
+    L.LizardGPU_planesXorStats.argtypes = [c.c_void_p]; L.LizardGPU_planesXorStats.restype = c.c_int
+    L.LizardGPU_tensorHeaderWrite3.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p]; L.LizardGPU_tensorHeaderWrite3.restype = c.c_size_t
+    L.LizardGPU_tensorHeaderRead3.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]; L.LizardGPU_tensorHeaderRead3.restype = c.c_int
     _lib = L
     return L
 

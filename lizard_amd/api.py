@@ -550,7 +550,9 @@ def decompress_stream_device(src, dst=None, size=None, verify_checksum=True):
 
 # ---- tensor streams: element bytes split into planes before compressing (include/lizard_amd.h Part 3c) ----
 
-TENSOR_HEADER_MAX = 8 + 40 + 8 * 8          # bytes of the longest tensor header (ndim = 8)
+TENSOR_HEADER_MAX = 8 + 40 + 8 * 8          # bytes of the longest "LZT1" / "LZT2" tensor header (ndim = 8)
+TENSOR_HEADER3_MAX = 8 + 48 + 8 * 8         # ... and of the longest "LZT3" header, the longest a reader meets
+TENSOR_XOR_BASE = 1                         # LIZARDGPU_TENSOR_XOR_BASE: the flag of an "LZT3" header
 
 
 FILTER_BYTE_PLANES, FILTER_BIT_PLANES = 0, 1   # LIZARDGPU_FILTER_*: what a tensor header says its data frame's bytes were split with
@@ -561,6 +563,12 @@ class _TensorDesc(ctypes.Structure):
     """LizardGPU_tensorDesc2_t: the v1 fields, then the filter."""
     _fields_ = [("elemSize", ctypes.c_uint32), ("ndim", ctypes.c_uint32), ("nbytes", ctypes.c_uint64), ("shape", ctypes.c_uint64 * 8),
                 ("dtype", ctypes.c_char * 24), ("filter", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class _TensorDesc3(ctypes.Structure):
+    """LizardGPU_tensorDesc3_t: the v2 fields with `reserved` named `flags`, then the base's tag."""
+    _fields_ = [("elemSize", ctypes.c_uint32), ("ndim", ctypes.c_uint32), ("nbytes", ctypes.c_uint64), ("shape", ctypes.c_uint64 * 8),
+                ("dtype", ctypes.c_char * 24), ("filter", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("baseTag", ctypes.c_uint64)]
 
 
 def _as_bytes(t):
@@ -578,9 +586,11 @@ def _plane_elem_size(t):
     return min(e, 8)
 
 
-def _planes_device(tensors, elem_sizes, join, filters=FILTER_BYTE_PLANES):
+def _planes_device(tensors, elem_sizes, join, filters=FILTER_BYTE_PLANES, bases=None, xor_entry=None):
     """`filters`: one LIZARDGPU_FILTER_* for all tensors or one per tensor; ONE launch per filter that occurs, all into one output
-    tensor."""
+    tensor.  `xor_entry` (one bool per tensor; None: none): the tensors that go through LizardGPU_splitPlanesXor_device /
+    LizardGPU_joinPlanesXor_device with bases[i] (None: no base) — one more launch per filter that occurs among THEM, into the same
+    output tensor; the others take the plain entries as before."""
     import torch
     L = _lib.lib()
     tensors = list(tensors)
@@ -596,7 +606,13 @@ def _planes_device(tensors, elem_sizes, join, filters=FILTER_BYTE_PLANES):
     assert len(elem_sizes) == n
     filters = [filters] * n if isinstance(filters, int) else [int(f) for f in filters]
     assert len(filters) == n and all(f in _PLANES_NAMES for f in filters)
+    xor_entry = [False] * n if xor_entry is None else [bool(x) for x in xor_entry]
+    bases = [None] * n if bases is None else list(bases)
+    assert len(xor_entry) == n and len(bases) == n
     sizes = [int(t.numel()) * t.element_size() for t in tensors]
+    for i, b in enumerate(bases):
+        if b is not None:
+            assert xor_entry[i] and b.is_cuda and b.is_contiguous() and b.device == device and int(b.numel()) * b.element_size() == sizes[i]
     offsets, total = [], 0
     for s in sizes:
         offsets.append(total)
@@ -606,12 +622,22 @@ def _planes_device(tensors, elem_sizes, join, filters=FILTER_BYTE_PLANES):
     stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
     for f in sorted(set(filters)):
         name = "LizardGPU_%s%sPlanes_device" % ("join" if join else "split", "Bit" if f == FILTER_BIT_PLANES else "")
-        pick = [i for i in range(n) if filters[i] == f]
+        pick = [i for i in range(n) if filters[i] == f and not xor_entry[i]]
         k = len(pick)
-        srcs = (ctypes.c_void_p * k)(*[tensors[i].data_ptr() for i in pick])
-        dsts = (ctypes.c_void_p * k)(*[out.data_ptr() + offsets[i] for i in pick])
-        _lib.check(getattr(L, name)(k, dsts, srcs, (ctypes.c_size_t * k)(*[sizes[i] for i in pick]),
-                                    (ctypes.c_uint32 * k)(*[elem_sizes[i] for i in pick]), stream), name)
+        if k:
+            srcs = (ctypes.c_void_p * k)(*[tensors[i].data_ptr() for i in pick])
+            dsts = (ctypes.c_void_p * k)(*[out.data_ptr() + offsets[i] for i in pick])
+            _lib.check(getattr(L, name)(k, dsts, srcs, (ctypes.c_size_t * k)(*[sizes[i] for i in pick]),
+                                        (ctypes.c_uint32 * k)(*[elem_sizes[i] for i in pick]), stream), name)
+        pick = [i for i in range(n) if filters[i] == f and xor_entry[i]]
+        k = len(pick)
+        if k:
+            name = "LizardGPU_%sPlanesXor_device" % ("join" if join else "split")
+            srcs = (ctypes.c_void_p * k)(*[tensors[i].data_ptr() for i in pick])
+            dsts = (ctypes.c_void_p * k)(*[out.data_ptr() + offsets[i] for i in pick])
+            xors = (ctypes.c_void_p * k)(*[None if bases[i] is None else bases[i].data_ptr() for i in pick])
+            _lib.check(getattr(L, name)(k, dsts, srcs, xors, (ctypes.c_size_t * k)(*[sizes[i] for i in pick]),
+                                        (ctypes.c_uint32 * k)(*[elem_sizes[i] for i in pick]), f, stream), name)
     return [out[o:o + s] for o, s in zip(offsets, sizes)]
 
 
@@ -645,7 +671,37 @@ def join_bit_planes_device(tensors, elem_sizes):
     return _planes_device(tensors, elem_sizes, True, FILTER_BIT_PLANES)
 
 
-def compress_tensors_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksum=False, split=True, planes="bytes"):
+def _planes_filter(planes, what):
+    if planes not in ("bytes", "bits"):
+        raise ValueError(f"{what}: planes={planes!r} is neither 'bytes' nor 'bits'")
+    return FILTER_BIT_PLANES if planes == "bits" else FILTER_BYTE_PLANES
+
+
+def split_planes_xor_device(tensors, bases, elem_sizes=None, planes="bytes"):
+    """split_planes_device (planes="bytes") or split_bit_planes_device (planes="bits") of `tensors` XOR `bases`, in ONE launch of
+    LizardGPU_splitPlanesXor_device on torch's current stream: every tensor's bytes are XORed with the bytes of its base in registers
+    on their way into the planes — no third buffer, 3 bytes of memory traffic per payload byte.  `bases`: a list as long as `tensors`
+    of contiguous CUDA tensors on the same device with the tensor's byte size, an earlier version of each tensor; bases[i] may be
+    None: tensor i is split as it is, in the same launch.  XOR against an earlier version turns every unchanged bit into a zero and
+    the planes put those zeros into runs: use it only against a base the data derives from (include/lizard_amd.h Part 3c has the
+    table).  Returns uint8 views into ONE output tensor, at 256-byte-aligned offsets."""
+    tensors, bases = list(tensors), list(bases)
+    if len(bases) != len(tensors):
+        raise ValueError(f"split_planes_xor_device: {len(bases)} bases for {len(tensors)} tensors")
+    return _planes_device(tensors, elem_sizes, False, _planes_filter(planes, "split_planes_xor_device"), bases, [True] * len(tensors))
+
+
+def join_planes_xor_device(tensors, bases, elem_sizes, planes="bytes"):
+    """The inverse of split_planes_xor_device for the same `bases`, `elem_sizes` and `planes`, in ONE launch of
+    LizardGPU_joinPlanesXor_device: join(tensor) XOR base; uint8 views into one output tensor, at 256-byte-aligned offsets."""
+    tensors, bases = list(tensors), list(bases)
+    if len(bases) != len(tensors):
+        raise ValueError(f"join_planes_xor_device: {len(bases)} bases for {len(tensors)} tensors")
+    return _planes_device(tensors, elem_sizes, True, _planes_filter(planes, "join_planes_xor_device"), bases, [True] * len(tensors))
+
+
+def compress_tensors_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksum=False, split=True, planes="bytes", base=None,
+                            base_tag=0):
     """A .liz STREAM for `tensors`, contiguous CUDA tensors of any dtype and shape on one device (zero-element ones and scalars
     allowed), as ONE uint8 CUDA tensor: per tensor a tensor header — a skippable frame with the dtype's name, the shape and the
     element size of the split (LizardGPU_tensorHeaderWrite) — and one frame with content size over the tensor's bytes SPLIT INTO
@@ -666,42 +722,66 @@ def compress_tensors_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, c
     LizardGPU_compressStream_device over all tensors with the headers as its prefixes (compress_stream_device_into), which writes
     every header and every frame once, to its place.  No payload byte crosses PCIe.
     Memory: the split bytes are a temporary of the size of the batch, beside the one allocation of LizardGPU_compressStreamBound bytes
-    of which the result is a view."""
+    of which the result is a view.
+    base (opt-in, per tensor; without it the call is what it was, byte for byte): a list as long as `tensors` whose entries are None
+    or a contiguous CUDA tensor on the same device with the tensor's dtype and shape (else ValueError naming the index) — an EARLIER
+    VERSION of the tensor that the reader will hold too: the previous checkpoint, the base model of a fine-tune.  The tensors with
+    a base, element size 1 included, go through ONE split_planes_xor_device launch (`planes` chooses the layout), which XORs each
+    with its base on the way into the planes — no temporary beyond the split buffer — and get an "LZT3" header
+    (LizardGPU_tensorHeaderWrite3) that holds `base_tag`, an opaque number of the caller's (a step number, a hash of their own)
+    by which a reader learns that it was handed the wrong base; the library does not hash bases.  The tensors without a base take
+    the path and the headers above.  Unchanged bits become zeros and the planes put them into runs: bf16 weights one Adam step of
+    lr 1e-5 behind their base are 0.31 of raw at level 10 and 0.15 at level 30 (0.84 / 0.75 without).  Use it only against a base
+    the data derives from: with an unrelated base it LOSES at level 10 with byte planes (0.91 against 0.84).  Readers of "LZT1" /
+    "LZT2" refuse "LZT3".  base with split=False raises ValueError."""
     L = _lib.lib()
     if planes not in ("bytes", "bits"):
         raise ValueError(f"compress_tensors_device: planes={planes!r} is neither 'bytes' nor 'bits'")
     if planes == "bits" and not split:
         raise ValueError("compress_tensors_device: planes='bits' with split=False (bit planes are a split)")
+    if base is not None and not split:
+        raise ValueError("compress_tensors_device: base with split=False (the XOR with a base is a filter of the split)")
     bits = planes == "bits"
     tensors = list(tensors)
     if not tensors:
         raise ValueError("compress_tensors_device: no tensors")
     device = tensors[0].device
+    base = [None] * len(tensors) if base is None else list(base)
+    if len(base) != len(tensors):
+        raise ValueError(f"compress_tensors_device: {len(base)} bases for {len(tensors)} tensors")
+    for i, (t, b) in enumerate(zip(tensors, base)):
+        if b is not None and (b.dtype != t.dtype or tuple(b.shape) != tuple(t.shape)):
+            raise ValueError(f"compress_tensors_device: tensor {i}: its base is {b.dtype} {tuple(b.shape)}, the tensor {t.dtype} {tuple(t.shape)}")
+        if b is not None and not (b.is_cuda and b.is_contiguous() and b.device == device):
+            raise ValueError(f"compress_tensors_device: tensor {i}: its base is not a contiguous CUDA tensor on {device}")
     descs = []
     for i, t in enumerate(tensors):
         assert t.is_cuda and t.is_contiguous() and t.device == device
         name = str(t.dtype).split(".")[-1].encode()
         if t.dim() > 8 or len(name) > 23:
             raise _lib.LizardAmdError(f"compress_tensors_device: tensor {i}: {t.dim()} dimensions / dtype {name.decode()} do not fit a tensor header")
-        d = _TensorDesc()
+        d = _TensorDesc3()
         d.elemSize, d.ndim, d.nbytes, d.dtype = (_plane_elem_size(t) if split else 1), t.dim(), int(t.numel()) * t.element_size(), name
         d.filter = FILTER_BIT_PLANES if bits else FILTER_BYTE_PLANES
+        if base[i] is not None:
+            d.flags, d.baseTag = TENSOR_XOR_BASE, int(base_tag)
         for k, s in enumerate(t.shape):
             d.shape[k] = int(s)
         descs.append(d)
     raw = [_as_bytes(t) for t in tensors]
-    wide = [i for i, d in enumerate(descs) if d.elemSize > 1]
-    if bits:
-        raw = split_bit_planes_device(raw, [d.elemSize for d in descs])
-    elif wide:
-        for i, p in zip(wide, split_planes_device([raw[i] for i in wide], [descs[i].elemSize for i in wide])):
+    # what is split: with bit planes every tensor, with byte planes those wider than a byte — and every tensor that has a base
+    wide = [i for i, d in enumerate(descs) if bits or d.elemSize > 1 or base[i] is not None]
+    if wide:
+        for i, p in zip(wide, _planes_device([raw[i] for i in wide], [descs[i].elemSize for i in wide], False, descs[0].filter,
+                                             [None if base[i] is None else _as_bytes(base[i]) for i in wide],
+                                             [base[i] is not None for i in wide])):
             raw[i] = p
-    host = np.zeros(len(descs) * TENSOR_HEADER_MAX, dtype=np.uint8)
+    host = np.zeros(len(descs) * TENSOR_HEADER3_MAX, dtype=np.uint8)
     at, headers = 0, []
     for i, d in enumerate(descs):
-        n = L.LizardGPU_tensorHeaderWrite2(host.ctypes.data + at, host.size - at, ctypes.byref(d))
+        n = L.LizardGPU_tensorHeaderWrite3(host.ctypes.data + at, host.size - at, ctypes.byref(d))
         if not n:
-            raise _lib.LizardAmdError(f"compress_tensors_device: tensor {i}: LizardGPU_tensorHeaderWrite2 refused the descriptor")
+            raise _lib.LizardAmdError(f"compress_tensors_device: tensor {i}: LizardGPU_tensorHeaderWrite3 refused the descriptor")
         headers.append(host[at:at + n].tobytes())
         at += n
     return compress_stream_device_into(raw, None, headers, level, block_size_id, checksum, True)[0]
@@ -724,13 +804,13 @@ def _tensor_stream_index(src, what):
         i += 2
     if not pairs:
         return []
-    takes = [min(h["frame_bytes"], TENSOR_HEADER_MAX) for h, _ in pairs]
+    takes = [min(h["frame_bytes"], TENSOR_HEADER3_MAX) for h, _ in pairs]
     index = np.concatenate([np.arange(h["offset"], h["offset"] + n, dtype=np.int64) for (h, _), n in zip(pairs, takes)])
     host = np.ascontiguousarray(src[torch.from_numpy(index).to(src.device)].cpu().numpy())
     out, at = [], 0
     for k, ((h, f), n) in enumerate(zip(pairs, takes)):
-        d, used = _TensorDesc(), ctypes.c_size_t(0)
-        rc = L.LizardGPU_tensorHeaderRead2(host.ctypes.data + at, n, ctypes.byref(d), ctypes.byref(used))
+        d, used = _TensorDesc3(), ctypes.c_size_t(0)
+        rc = L.LizardGPU_tensorHeaderRead3(host.ctypes.data + at, n, ctypes.byref(d), ctypes.byref(used))
         if rc or used.value != h["frame_bytes"]:
             raise _lib.LizardAmdError(f"{what}: tensor {k}: the skippable frame at offset {h['offset']} in front of the data frame is not a "
                                       f"tensor header, so the data frame at offset {f['offset']} has no tensor header in front of it")
@@ -742,15 +822,17 @@ def _tensor_stream_index(src, what):
 def tensors_info_device(stream):
     """What the tensor stream in `stream` (a contiguous uint8 CUDA tensor, what compress_tensors_device returns) holds, without
     decoding anything: one dict per tensor with dtype (its name), shape, planes ("bytes" or "bits": the filter), elem_size (of the
-    split; with "bytes", 1 = stored unsplit), nbytes, offset (of the tensor's header in the stream), header_bytes and frame_bytes (of the data frame behind the header).  Raises
+    split; with "bytes", 1 = stored unsplit), nbytes, offset (of the tensor's header in the stream), header_bytes and frame_bytes (of the data frame behind the header),
+    xor_base (bool: an "LZT3" header — the tensor was XORed with a base, which decompress_tensors_device needs) and base_tag (the
+    number the writer stored for that base; 0 without one).  Raises
     LizardAmdError naming the tensor's index for a data frame without a tensor header in front of it."""
     return [{"dtype": d.dtype.decode(), "shape": tuple(int(s) for s in d.shape[:d.ndim]), "planes": _PLANES_NAMES[int(d.filter)],
-             "elem_size": int(d.elemSize), "nbytes": int(d.nbytes),
+             "elem_size": int(d.elemSize), "nbytes": int(d.nbytes), "xor_base": bool(d.flags & TENSOR_XOR_BASE), "base_tag": int(d.baseTag),
              "offset": h["offset"], "header_bytes": h["frame_bytes"], "frame_bytes": f["frame_bytes"]}
             for h, f, d in _tensor_stream_index(stream, "tensors_info_device")]
 
 
-def decompress_tensors_device(stream, verify_checksum=True):
+def decompress_tensors_device(stream, verify_checksum=True, base=None, base_tag=None):
     """The tensors of the tensor stream in `stream`, a contiguous uint8 CUDA tensor (what compress_tensors_device returns), with dtype
     and shape restored: a list of views into ONE allocation, each 256-byte aligned.  In this order: one stream_info_device, one
     indexed read of all header bytes, one decompress_stream_device — ONE decode batch for a stream of this library, because the headers
@@ -761,10 +843,21 @@ def decompress_tensors_device(stream, verify_checksum=True):
     skippable frame that is none), when a header's nbytes differs from its frame's decoded size (a data frame with records must
     carry its content size), when the shape does not make nbytes, or when torch does not know the dtype's name; a frame the decoder
     refuses raises as in decompress_stream_device.
-    Memory: the decoded, still split bytes are a temporary of the size of the batch beside the result."""
+    Memory: the decoded, still split bytes are a temporary of the size of the batch beside the result.
+    base: what compress_tensors_device was given — a list indexed by the tensor's position in the stream, as long as the stream has
+    tensors (else ValueError), of None or a contiguous CUDA tensor on the stream's device.  A tensor with an "LZT3" header is joined
+    and XORed with its base (join_planes_xor_device's kernel: one more launch per filter that occurs among such tensors, into the
+    same result); a stream without one takes exactly the path above.  Raises LizardAmdError naming the tensor's index when an
+    "LZT3" tensor has no base, when its base's byte size or dtype is not the header's, or when `base_tag` is given and differs
+    from the header's.  A base handed for a tensor whose header is not "LZT3" is IGNORED.  The library cannot tell a wrong base
+    of the right size and tag: the tensor then comes back wrong, silently — the tag is the caller's guard."""
     import torch
     what = "decompress_tensors_device"
     entries = _tensor_stream_index(stream, what)
+    if base is not None:
+        base = list(base)
+        if len(base) != len(entries):
+            raise ValueError(f"{what}: {len(base)} bases for a stream of {len(entries)} tensors")
     if not entries:
         return []
     dtypes = []
@@ -781,6 +874,17 @@ def decompress_tensors_device(stream, verify_checksum=True):
         if count * torch.empty(0, dtype=dt).element_size() != d.nbytes:
             raise _lib.LizardAmdError(f"{what}: tensor {k}: shape {tuple(d.shape[:d.ndim])} of {d.dtype.decode()} is not {d.nbytes} bytes")
         dtypes.append(dt)
+        if d.flags & TENSOR_XOR_BASE:
+            b = None if base is None else base[k]
+            if b is None:
+                raise _lib.LizardAmdError(f"{what}: tensor {k}: its header says it was XORed with a base (tag {d.baseTag}), and none was given")
+            if int(b.numel()) * b.element_size() != d.nbytes or b.dtype != dt:
+                raise _lib.LizardAmdError(f"{what}: tensor {k}: its base is {int(b.numel()) * b.element_size()} bytes of {b.dtype}, "
+                                          f"the header says {d.nbytes} bytes of {dt}")
+            if base_tag is not None and int(base_tag) != d.baseTag:
+                raise _lib.LizardAmdError(f"{what}: tensor {k}: the header holds base tag {d.baseTag}, the caller gave {int(base_tag)}")
+            if not (b.is_cuda and b.is_contiguous() and b.device == stream.device):
+                raise _lib.LizardAmdError(f"{what}: tensor {k}: its base is not a contiguous CUDA tensor on {stream.device}")
     total = sum(int(d.nbytes) for _, _, d in entries)
     decoded, _ = decompress_stream_device(stream, size=total, verify_checksum=verify_checksum)
     if int(decoded.numel()) != total:
@@ -789,5 +893,7 @@ def decompress_tensors_device(stream, verify_checksum=True):
     for _, _, d in entries:
         pieces.append(decoded[pos:pos + int(d.nbytes)])
         pos += int(d.nbytes)
-    joined = _planes_device(pieces, [int(d.elemSize) for _, _, d in entries], True, [int(d.filter) for _, _, d in entries])
+    xored = [bool(d.flags & TENSOR_XOR_BASE) for _, _, d in entries]
+    joined = _planes_device(pieces, [int(d.elemSize) for _, _, d in entries], True, [int(d.filter) for _, _, d in entries],
+                            [_as_bytes(base[k]) if x else None for k, x in enumerate(xored)] if any(xored) else None, xored)
     return [b.view(dt).reshape(tuple(int(s) for s in d.shape[:d.ndim])) for b, dt, (_, _, d) in zip(joined, dtypes, entries)]

@@ -31,6 +31,9 @@
 // bit (one lane per plane byte, or per element byte), and the bytes behind n8 * E byte by byte, in the buffer's last tile.
 // The 16-byte accesses need no alignment (plane k starts at dst + k * P).
 //
+// XOR with a base (lz_bitplanes_xor_tile; planes_kernels.h has the semantics and the entry): the lane loads from the base the 2 E
+// pieces of 16 bytes of the interleaved side that it loads from src (split) or is about to store (join), with the loads of the step.
+//
 // The bodies are written against lz_wave.h alone, so the CPU SIMT emulator of tests/emul runs them unchanged; the quad exchange
 // (lzb_quad_xor1 / lzb_quad_xor2: DPP on the device) has a plain form on lz_shfl there.
 #ifndef BITPLANES_KERNELS_H
@@ -124,20 +127,36 @@ LZ_DEV void lzb_quad_transpose(u32* a)
 // one wave call and stay together (the quad exchange); e0, e1, P are wave-uniform.  A quad past e1 takes part with zeros and
 // touches no memory.  Every register is stored as soon as it is made: the source needs 8 E + 8 registers alive, not twice 8 E
 // (the compiler's schedule keeps more: DESIGN.md 8.1 has the counts).
-template <u32 E, bool JOIN>
-LZ_DEV void lzb_move(const u8* src, u8* dst, u64 P, u64 e0, u64 e1)
+// XOR: xb is the buffer's base (LzPlanesXorEntry), interleaved bytes.  The lane loads from xb the 2 E pieces of 16 bytes that it
+// loads from src (split) or is about to store (join: for E >= 2 those are the pieces of the quad it holds after the exchange of
+// pieces), together with the source loads of the step, and XORs them in registers: into the source before the transpose, into
+// every piece just before its store.
+template <u32 E, bool JOIN, bool XOR = false>
+LZ_DEV void lzb_move(const u8* src, u8* dst, u64 P, u64 e0, u64 e1, const u8* xb = nullptr)
 {
     const u32 lane = lz_lane(), q = lane >> 2, r = lane & 3u;
+    constexpr u32 H = E / 2;                                       // groups of four pieces in a lane (the join's exchange of pieces)
     for (u64 base = e0; base < e1; base += LZB_STEP_ELEMS) {
         const bool whole = base + (u64)LZB_QUAD_ELEMS * (q + 1) <= e1;
         const u8* const s = src + (JOIN ? r * P + base / 8 + 16 * q : (base + LZB_LANE_ELEMS * lane) * E);
         u8* const d = dst + (JOIN ? (base + LZB_LANE_ELEMS * lane) * E : r * P + base / 8 + 16 * q);
         u32 in[8 * E];                                             // interleaved: the lane's 32 E bytes; planar: 16 bytes of 2 E planes
+        u32 bx[XOR ? 8 * E : 1];                                   // the base's pieces, in the order of the loads (split) or stores (join)
 #pragma unroll
         for (u32 m = 0; m < 8 * E; m++) in[m] = 0;
         if (whole) {
 #pragma unroll
             for (u32 m = 0; m < 2 * E; m++) lzp_ld16(s + (JOIN ? 4 * m * P : 16 * m), in + 4 * m);
+            if constexpr (XOR) {
+                // where the lane's piece m lies on the interleaved side: its own 32 E bytes, or (join, E >= 2) piece 4 i + r of the quad's
+                const u8* const x = xb + ((JOIN && E >= 2) ? (base + (u64)LZB_QUAD_ELEMS * q) * E + 16 * r : (base + LZB_LANE_ELEMS * lane) * E);
+#pragma unroll
+                for (u32 m = 0; m < 2 * E; m++) lzp_ld16(x + ((JOIN && E >= 2) ? 64 * m : 16 * m), bx + 4 * m);
+                if constexpr (!JOIN) {
+#pragma unroll
+                    for (u32 m = 0; m < 8 * E; m++) in[m] ^= bx[m];
+                }
+            }
         }
         if constexpr (!JOIN) {
 #pragma unroll
@@ -163,14 +182,19 @@ LZ_DEV void lzb_move(const u8* src, u8* dst, u64 P, u64 e0, u64 e1)
                 for (u32 m = 0; m < 2; m++) {
                     u32 out[4];
                     lzb_from_planes<E>(in, m, out);
-                    if (whole) lzp_st16(d + 16 * m, out);
+                    if (whole) {
+                        if constexpr (XOR) {
+#pragma unroll
+                            for (u32 k = 0; k < 4; k++) out[k] ^= bx[4 * m + k];
+                        }
+                        lzp_st16(d + 16 * m, out);
+                    }
                 }
             } else {
                 // The lane's 32 E bytes are 2 E pieces of 16 bytes.  Stored as they are, a store instruction would put 16 bytes into
                 // every 32 E: eight instructions to fill one cache line for E = 4.  So the quad exchanges pieces, four at a time (a
                 // 4 x 4 transpose of pieces: four of dwords), and lane r stores piece 4 i + r of the QUAD's 128 E bytes: every
                 // store instruction writes runs of 64 contiguous bytes.
-                constexpr u32 H = E / 2;                           // groups of four pieces in a lane
                 u8* const dq = dst + (base + (u64)LZB_QUAD_ELEMS * q) * E + 16 * r;
 #pragma unroll
                 for (u32 h = 0; h < H; h++) {
@@ -185,6 +209,12 @@ LZ_DEV void lzb_move(const u8* src, u8* dst, u64 P, u64 e0, u64 e1)
                         for (u32 c = 0; c < 4; c++) t[c][k] = a[c];
                     }
                     if (whole) {
+                        if constexpr (XOR) {
+#pragma unroll
+                            for (u32 c = 0; c < 4; c++)
+#pragma unroll
+                                for (u32 k = 0; k < 4; k++) t[c][k] ^= bx[4 * (c * H + h) + k];
+                        }
 #pragma unroll
                         for (u32 c = 0; c < 4; c++) lzp_st16(dq + 64 * (c * H + h), t[c]);
                     }
@@ -196,8 +226,8 @@ LZ_DEV void lzb_move(const u8* src, u8* dst, u64 P, u64 e0, u64 e1)
 
 // The ragged end of the planes, elements [n128, n8) (fewer than 128, a multiple of 8), bit by bit: split, a lane per plane byte;
 // join, a lane per element byte.  No lane waits for another.
-template <u32 E, bool JOIN>
-LZ_DEV void lzb_ragged(const u8* src, u8* dst, u64 P, u64 n128, u64 n8)
+template <u32 E, bool JOIN, bool XOR = false>
+LZ_DEV void lzb_ragged(const u8* src, u8* dst, u64 P, u64 n128, u64 n8, const u8* xb = nullptr)
 {
     const u32 lane = lz_lane(), R = (u32)(n8 - n128) / 8;          // bytes at the end of every plane: 0 .. 15
     if constexpr (!JOIN) {
@@ -205,7 +235,10 @@ LZ_DEV void lzb_ragged(const u8* src, u8* dst, u64 P, u64 n128, u64 n8)
         if (j < R)
             for (u32 k = lane >> 4; k < 8 * E; k += 4) {
                 u32 v = 0;
-                for (u32 b = 0; b < 8; b++) v |= ((lzp_ld8(src + (n128 + 8 * j + b) * E + k / 8) >> (k % 8)) & 1u) << b;
+                for (u32 b = 0; b < 8; b++) {
+                    const u64 at = (n128 + 8 * j + b) * E + k / 8;
+                    v |= (((lzp_ld8(src + at) ^ (XOR ? lzp_ld8(xb + at) : 0u)) >> (k % 8)) & 1u) << b;
+                }
                 lzp_st8(dst + k * P + n128 / 8 + j, v);
             }
     } else {
@@ -214,22 +247,22 @@ LZ_DEV void lzb_ragged(const u8* src, u8* dst, u64 P, u64 n128, u64 n8)
             const u32 p = x % E;
             u32 v = 0;
             for (u32 b = 0; b < 8; b++) v |= ((lzp_ld8(src + (8 * p + b) * P + i / 8) >> (u32)(i % 8)) & 1u) << b;
-            lzp_st8(dst + i * E + p, v);
+            lzp_st8(dst + i * E + p, v ^ (XOR ? lzp_ld8(xb + i * E + p) : 0u));
         }
     }
 }
 
-template <u32 E, bool JOIN>
-LZ_DEV void lzb_tile(const u8* src, u8* dst, u64 size, u32 t)
+template <u32 E, bool JOIN, bool XOR = false>
+LZ_DEV void lzb_tile(const u8* src, u8* dst, u64 size, u32 t, const u8* xb = nullptr)
 {
     const u64 n = size / E, n8 = n & ~(u64)7, n128 = n & ~(u64)(LZB_QUAD_ELEMS - 1), P = n8 / 8;
     const u64 e0 = (u64)t * (LZP_TILE_BYTES / E);
     const u64 e1 = e0 + LZP_TILE_BYTES / E < n ? e0 + LZP_TILE_BYTES / E : n;
-    lzb_move<E, JOIN>(src, dst, P, e0, e1 < n128 ? e1 : n128);
+    lzb_move<E, JOIN, XOR>(src, dst, P, e0, e1 < n128 ? e1 : n128, xb);
     if (e1 == n) {                                                 // the buffer's last tile: the ragged end and the copied bytes
-        lzb_ragged<E, JOIN>(src, dst, P, n128, n8);
+        lzb_ragged<E, JOIN, XOR>(src, dst, P, n128, n8, xb);
         const u64 at = n8 * E + lz_lane();                         // fewer than 8 E bytes
-        if (at < size) lzp_st8(dst + at, lzp_ld8(src + at));
+        if (at < size) lzp_st8(dst + at, lzp_ld8(src + at) ^ (XOR ? lzp_ld8(xb + at) : 0u));
     }
 }
 
@@ -249,6 +282,29 @@ LZ_DEV void lz_bitplanes_tile(const LzPlanesEntry* tab, u32 nEntries, u32 tileOf
     else lzb_tile<1, JOIN>(src, dst, size, t);
 }
 
+// ... of a batch with bases (LzPlanesXorEntry, lzp_xor_entry_of): an entry without a base takes the plain path on a wave-uniform
+// branch.
+template <bool JOIN, bool XOR>
+LZ_DEV void lzb_tile_of(const u8* src, u8* dst, u64 size, u32 E, u32 t, const u8* xb)
+{
+    if (E == 2) lzb_tile<2, JOIN, XOR>(src, dst, size, t, xb);
+    else if (E == 4) lzb_tile<4, JOIN, XOR>(src, dst, size, t, xb);
+    else if (E == 8) lzb_tile<8, JOIN, XOR>(src, dst, size, t, xb);
+    else lzb_tile<1, JOIN, XOR>(src, dst, size, t, xb);
+}
+
+template <bool JOIN>
+LZ_DEV void lz_bitplanes_xor_tile(const LzPlanesXorEntry* tab, u32 nEntries, u32 tileOfWave)
+{
+    const u32 tile = lz_uniform(tileOfWave);
+    const LzPlanesXorEntry* const e = lzp_xor_entry_of(tab, nEntries, tile);
+    const u8* const src = (const u8*)(uintptr_t)e->src;
+    u8* const dst = (u8*)(uintptr_t)e->dst;
+    const u8* const xb = (const u8*)(uintptr_t)e->base;
+    if (xb) lzb_tile_of<JOIN, true>(src, dst, e->size, e->elem, tile - e->firstTile, xb);
+    else lzb_tile_of<JOIN, false>(src, dst, e->size, e->elem, tile - e->firstTile, nullptr);
+}
+
 #ifdef __HIPCC__
 template <bool JOIN>
 LZ_DEV void lz_bitplanes_grid(const LzPlanesEntry* tab, u32 nEntries, u32 nTiles)
@@ -264,6 +320,21 @@ __global__ __launch_bounds__(64 * LZP_WAVES) void lz_bitplanes_split_kernel(cons
 __global__ __launch_bounds__(64 * LZP_WAVES) void lz_bitplanes_join_kernel(const LzPlanesEntry* tab, u32 nEntries, u32 nTiles)
 {
     lz_bitplanes_grid<true>(tab, nEntries, nTiles);
+}
+template <bool JOIN>
+LZ_DEV void lz_bitplanes_xor_grid(const LzPlanesXorEntry* tab, u32 nEntries, u32 nTiles)
+{
+    const u64 stride = (u64)gridDim.x * LZP_WAVES;
+    for (u64 tile = (u64)blockIdx.x * LZP_WAVES + threadIdx.x / 64; tile < nTiles; tile += stride)
+        lz_bitplanes_xor_tile<JOIN>(tab, nEntries, (u32)tile);
+}
+__global__ __launch_bounds__(64 * LZP_WAVES) void lz_bitplanes_xor_split_kernel(const LzPlanesXorEntry* tab, u32 nEntries, u32 nTiles)
+{
+    lz_bitplanes_xor_grid<false>(tab, nEntries, nTiles);
+}
+__global__ __launch_bounds__(64 * LZP_WAVES) void lz_bitplanes_xor_join_kernel(const LzPlanesXorEntry* tab, u32 nEntries, u32 nTiles)
+{
+    lz_bitplanes_xor_grid<true>(tab, nEntries, nTiles);
 }
 #endif
 #endif  /* __cplusplus */

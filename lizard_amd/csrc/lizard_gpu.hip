@@ -928,6 +928,19 @@ int   lzk_planes_launch(LzCtx* c, const LzPlanesEntry* d_tab, uint32_t nEntries,
     LZ_HIP(hipGetLastError());
     return 0;
 }
+int   lzk_planes_xor_launch(LzCtx* c, const LzPlanesXorEntry* d_tab, uint32_t nEntries, uint32_t nTiles, int join, int bits, hipStream_t stream)
+{
+    static_assert(sizeof(LzPlanesXorEntry) == 40, "the table the host file fills");
+    if (!d_tab || nEntries == 0 || nTiles == 0) { snprintf(t_err, sizeof t_err, "bad argument (null pointer or no tiles)"); return -LIZARDGPU_ERR_ARG; }
+    // the grid of lzk_planes_launch
+    const u32 groups = (nTiles + LZP_WAVES - 1u) / LZP_WAVES, cap = (u32)c->cus * 8u;
+    const dim3 grid(groups < cap ? groups : cap), block(64 * LZP_WAVES);
+    void (*const kernel)(const LzPlanesXorEntry*, u32, u32) = bits ? (join ? lz_bitplanes_xor_join_kernel : lz_bitplanes_xor_split_kernel)
+                                                                   : (join ? lz_planes_xor_join_kernel : lz_planes_xor_split_kernel);
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, d_tab, nEntries, nTiles);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
 
 #ifdef LZ_PROFILE
 // Profile builds only: sum of the per-wave phase clocks since the last call (scratch slot tails), then reset.

@@ -92,6 +92,7 @@ typedef struct LzCtx {
     unsigned long long devStreamCompressStats[4];  /* LizardGPU_streamCompressDeviceStats (lizard_stream_device.c); since process start */
     unsigned long long devPlanesStats[4];          /* LizardGPU_planesStats (lizard_planes_device.c); since process start */
     unsigned long long devBitPlanesStats[4];       /* LizardGPU_bitPlanesStats (lizard_planes_device.c); since process start */
+    unsigned long long devPlanesXorStats[4];       /* LizardGPU_planesXorStats (lizard_planes_device.c); since process start */
     LzStage stage[LZ_STAGES];
     LzCombine comb;
     pthread_mutex_t mu;
@@ -227,6 +228,9 @@ int   lzk_unstream_walk_launch(const void* d_src, size_t srcSize, struct LzStrea
  * batch's nEntries non-empty buffers, whose table lies at d_tab */
 struct LzPlanesEntry;
 int   lzk_planes_launch(LzCtx* c, const struct LzPlanesEntry* d_tab, uint32_t nEntries, uint32_t nTiles, int join, int bits, hipStream_t stream);
+/* LizardGPU_splitPlanesXor_device / LizardGPU_joinPlanesXor_device: the same launch over a table of entries with a base each */
+struct LzPlanesXorEntry;
+int   lzk_planes_xor_launch(LzCtx* c, const struct LzPlanesXorEntry* d_tab, uint32_t nEntries, uint32_t nTiles, int join, int bits, hipStream_t stream);
 /* lizard_pipeline_host.c: its staging helpers, shared with lizard_unframe_host.c */
 int    lzp_ensure_dev(LzCtx* c, void** p, size_t* cap, size_t need);
 int    lzp_ensure_pinned(void** p, size_t* cap, size_t need);

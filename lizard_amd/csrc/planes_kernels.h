@@ -25,6 +25,13 @@
 // The transpose is lzp_perm picks (v_perm_b32: any four of the eight bytes of two registers): one per output register for E = 2,
 // three for E = 4 and 8 — 0.75 VALU instructions per byte at most, two orders of magnitude below what the memory side delivers.
 //
+//
+// XOR with a base (LizardGPU_splitPlanesXor_device / LizardGPU_joinPlanesXor_device, lz_planes_xor_tile).  A buffer may come with an
+// earlier version of its `size` INTERLEAVED bytes, its base, at any byte address: split writes split(src XOR base), join writes
+// join(src) XOR base, every byte taking part (the ragged end and the tail too).  The lane loads from the base the E pieces of 16
+// bytes of its interleaved side together with the loads of the step — one memory trip — and XORs in registers: 3 bytes of memory
+// traffic per payload byte.  The plain kernels are the XOR = false instantiations of the same bodies and compile to what they were.
+//
 // The bodies are written against lz_wave.h alone, so the CPU SIMT emulator of tests/emul runs them unchanged (lzp_perm has a
 // plain-C form there).
 #ifndef PLANES_KERNELS_H
@@ -35,6 +42,11 @@
 
 /* One non-empty buffer of the batch, in device memory.  firstTile: the number of its first tile in the batch. */
 typedef struct LzPlanesEntry { uint64_t src, dst, size; uint32_t elem, firstTile; } LzPlanesEntry;
+
+/* ... of LizardGPU_splitPlanesXor_device / LizardGPU_joinPlanesXor_device: split writes dst = split(src XOR base), join writes
+ * dst = join(src) XOR base, with `base` an earlier version of the INTERLEAVED bytes, `size` of them, at any byte address.
+ * base == 0: this buffer has none and its tiles take the plain path. */
+typedef struct LzPlanesXorEntry { uint64_t src, dst, base, size; uint32_t elem, firstTile; } LzPlanesXorEntry;
 
 #ifdef __cplusplus
 #include "lz_wave.h"
@@ -94,35 +106,58 @@ LZ_DEV void lzp_st8(u8* p, u32 v) { lz_st8_s(p, v); }
 #endif
 
 // Elements [e0, e1) of a buffer of n elements, e0 a multiple of 1 024: all lanes of one wave call; e0, e1, n are wave-uniform.
-template <u32 E, bool JOIN>
-LZ_DEV void lzp_move(const u8* src, u8* dst, u64 n, u64 e0, u64 e1)
+// XOR: xb is the buffer's base (LzPlanesXorEntry), the interleaved bytes of an earlier version: the lane loads the 16-byte pieces of
+// its 16 E interleaved bytes from xb as well — together with the loads of the step, one memory trip for both — and XORs them in
+// registers, before the transpose (split) or behind it (join).
+template <u32 E, bool JOIN, bool XOR = false>
+LZ_DEV void lzp_move(const u8* src, u8* dst, u64 n, u64 e0, u64 e1, const u8* xb = nullptr)
 {
     const u32 lane = lz_lane();
     for (u64 base = e0; base < e1; base += 64 * 16) {
         const u64 i = base + 16 * lane;                            // the lane's first element
         if (i + 16 <= n) {
-            u32 in[4 * E], out[4 * E];
+            u32 in[4 * E], out[4 * E], bx[XOR ? 4 * E : 1];
             if constexpr (E == 1) {
                 lzp_ld16(src + i, in);
+                if constexpr (XOR) {
+                    lzp_ld16(xb + i, bx);
+#pragma unroll
+                    for (u32 m = 0; m < 4; m++) in[m] ^= bx[m];
+                }
                 lzp_st16(dst + i, in);
             } else if constexpr (!JOIN) {
 #pragma unroll
                 for (u32 q = 0; q < E; q++) lzp_ld16(src + i * E + 16 * q, in + 4 * q);
+                if constexpr (XOR) {
+#pragma unroll
+                    for (u32 q = 0; q < E; q++) lzp_ld16(xb + i * E + 16 * q, bx + 4 * q);
+#pragma unroll
+                    for (u32 m = 0; m < 4 * E; m++) in[m] ^= bx[m];
+                }
                 lzp_transpose16<E, false>(in, out);
 #pragma unroll
                 for (u32 p = 0; p < E; p++) lzp_st16(dst + p * n + i, out + 4 * p);
             } else {
 #pragma unroll
                 for (u32 p = 0; p < E; p++) lzp_ld16(src + p * n + i, in + 4 * p);
+                if constexpr (XOR) {
+#pragma unroll
+                    for (u32 q = 0; q < E; q++) lzp_ld16(xb + i * E + 16 * q, bx + 4 * q);
+                }
                 lzp_transpose16<E, true>(in, out);
+                if constexpr (XOR) {
+#pragma unroll
+                    for (u32 m = 0; m < 4 * E; m++) out[m] ^= bx[m];
+                }
 #pragma unroll
                 for (u32 q = 0; q < E; q++) lzp_st16(dst + i * E + 16 * q, out + 4 * q);
             }
         } else {
             for (u64 j = i; j < n; j++)                            // the ragged end of the planes: fewer than 16 elements, one lane
                 for (u32 p = 0; p < E; p++) {
-                    if (!JOIN) lzp_st8(dst + p * n + j, lzp_ld8(src + j * E + p));
-                    else lzp_st8(dst + j * E + p, lzp_ld8(src + p * n + j));
+                    const u32 x = XOR ? lzp_ld8(xb + j * E + p) : 0u;
+                    if (!JOIN) lzp_st8(dst + p * n + j, lzp_ld8(src + j * E + p) ^ x);
+                    else lzp_st8(dst + j * E + p, lzp_ld8(src + p * n + j) ^ x);
                 }
         }
     }
@@ -140,27 +175,54 @@ LZ_DEV const LzPlanesEntry* lzp_entry_of(const LzPlanesEntry* tab, u32 nEntries,
     return tab + lo;
 }
 
+// Tile t of one buffer: all lanes of one wave call; every argument is wave-uniform.
+template <bool JOIN, bool XOR = false>
+LZ_DEV void lzp_tile(const u8* src, u8* dst, u64 size, u32 E, u32 t, const u8* xb = nullptr)
+{
+    const u64 n = size / E;
+    const u64 e0 = (u64)t * (LZP_TILE_BYTES / E);
+    const u64 e1 = e0 + LZP_TILE_BYTES / E < n ? e0 + LZP_TILE_BYTES / E : n;
+    if (E == 2) lzp_move<2, JOIN, XOR>(src, dst, n, e0, e1, xb);
+    else if (E == 4) lzp_move<4, JOIN, XOR>(src, dst, n, e0, e1, xb);
+    else if (E == 8) lzp_move<8, JOIN, XOR>(src, dst, n, e0, e1, xb);
+    else lzp_move<1, JOIN, XOR>(src, dst, n, e0, e1, xb);
+    if (t == 0) {                                                  // the bytes behind the last whole element: fewer than E
+        const u64 at = n * E + lz_lane();
+        if (at < size) lzp_st8(dst + at, lzp_ld8(src + at) ^ (XOR ? lzp_ld8(xb + at) : 0u));
+    }
+}
+
 // Tile `tile` (< the batch's tile count) of the batch: all lanes of one wave call; everything but the lane's share is wave-uniform.
 template <bool JOIN>
 LZ_DEV void lz_planes_tile(const LzPlanesEntry* tab, u32 nEntries, u32 tileOfWave)
 {
     const u32 tile = lz_uniform(tileOfWave);                       // in SGPRs: the bisection and the entry are scalar loads
     const LzPlanesEntry* const e = lzp_entry_of(tab, nEntries, tile);
+    lzp_tile<JOIN>((const u8*)(uintptr_t)e->src, (u8*)(uintptr_t)e->dst, e->size, e->elem, tile - e->firstTile);
+}
+
+// ... of a batch with bases: lzp_entry_of for the 40-byte entry, and the tile.  An entry without a base takes the plain path on a
+// wave-uniform branch, so a mixed batch is one launch.  Shared with bitplanes_kernels.h.
+LZ_DEV const LzPlanesXorEntry* lzp_xor_entry_of(const LzPlanesXorEntry* tab, u32 nEntries, u32 tile)
+{
+    u32 lo = 0, hi = nEntries;
+    while (hi - lo > 1) {
+        const u32 mid = lo + (hi - lo) / 2;
+        if (tab[mid].firstTile <= tile) lo = mid; else hi = mid;
+    }
+    return tab + lo;
+}
+
+template <bool JOIN>
+LZ_DEV void lz_planes_xor_tile(const LzPlanesXorEntry* tab, u32 nEntries, u32 tileOfWave)
+{
+    const u32 tile = lz_uniform(tileOfWave);
+    const LzPlanesXorEntry* const e = lzp_xor_entry_of(tab, nEntries, tile);
     const u8* const src = (const u8*)(uintptr_t)e->src;
     u8* const dst = (u8*)(uintptr_t)e->dst;
-    const u64 size = e->size;
-    const u32 E = e->elem, t = tile - e->firstTile;
-    const u64 n = size / E;
-    const u64 e0 = (u64)t * (LZP_TILE_BYTES / E);
-    const u64 e1 = e0 + LZP_TILE_BYTES / E < n ? e0 + LZP_TILE_BYTES / E : n;
-    if (E == 2) lzp_move<2, JOIN>(src, dst, n, e0, e1);
-    else if (E == 4) lzp_move<4, JOIN>(src, dst, n, e0, e1);
-    else if (E == 8) lzp_move<8, JOIN>(src, dst, n, e0, e1);
-    else lzp_move<1, JOIN>(src, dst, n, e0, e1);
-    if (t == 0) {                                                  // the bytes behind the last whole element: fewer than E
-        const u64 at = n * E + lz_lane();
-        if (at < size) lzp_st8(dst + at, lzp_ld8(src + at));
-    }
+    const u8* const xb = (const u8*)(uintptr_t)e->base;
+    if (xb) lzp_tile<JOIN, true>(src, dst, e->size, e->elem, tile - e->firstTile, xb);
+    else lzp_tile<JOIN>(src, dst, e->size, e->elem, tile - e->firstTile);
 }
 
 #ifdef __HIPCC__
@@ -179,6 +241,21 @@ __global__ __launch_bounds__(64 * LZP_WAVES) void lz_planes_split_kernel(const L
 __global__ __launch_bounds__(64 * LZP_WAVES) void lz_planes_join_kernel(const LzPlanesEntry* tab, u32 nEntries, u32 nTiles)
 {
     lz_planes_grid<true>(tab, nEntries, nTiles);
+}
+template <bool JOIN>
+LZ_DEV void lz_planes_xor_grid(const LzPlanesXorEntry* tab, u32 nEntries, u32 nTiles)
+{
+    const u64 stride = (u64)gridDim.x * LZP_WAVES;
+    for (u64 tile = (u64)blockIdx.x * LZP_WAVES + threadIdx.x / 64; tile < nTiles; tile += stride)
+        lz_planes_xor_tile<JOIN>(tab, nEntries, (u32)tile);
+}
+__global__ __launch_bounds__(64 * LZP_WAVES) void lz_planes_xor_split_kernel(const LzPlanesXorEntry* tab, u32 nEntries, u32 nTiles)
+{
+    lz_planes_xor_grid<false>(tab, nEntries, nTiles);
+}
+__global__ __launch_bounds__(64 * LZP_WAVES) void lz_planes_xor_join_kernel(const LzPlanesXorEntry* tab, u32 nEntries, u32 nTiles)
+{
+    lz_planes_xor_grid<true>(tab, nEntries, nTiles);
 }
 #endif
 #endif  /* __cplusplus */
