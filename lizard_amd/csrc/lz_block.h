@@ -115,6 +115,19 @@ LZ_DEV u32 lz_hash5_plain(u64 u) { return (u32)(((u * 889523592379ULL) << 24) >>
 // function of those four bytes serves (equal bytes => equal bits, fast.h:97 is the test that counts); this one costs nothing,
 // it is a partial product of the hash.
 LZ_DEV u32 lz_check_mix(u32 first4) { return first4 * LZ_HASH5_KHI; }
+// LzTab's seven check bits, in place (bits 17..23 of an entry): bits LZ_CHECK_LO .. LZ_CHECK_LO + 6 of that product.  The slot index is
+// the top HASHLOG bits of a sum that this product dominates, so among the entries that meet in one slot the product's top bits are
+// nearly equal already and say little; a field below the index is as good as independent of it (profiles/count_trip_ab.txt: failed
+// 4-byte tests per eligible probe 1/92 with the top seven bits, LZ_CHECK_LO = 25, on the bench data).  A shift and a mask either way.
+// The check bits never reach the output.
+#ifndef LZ_CHECK_LO
+#define LZ_CHECK_LO 13
+#endif
+LZ_DEV u32 lz_check7(u32 mix)
+{
+    static_assert(LZ_CHECK_LO >= 0 && LZ_CHECK_LO <= 25, "seven bits of a 32-bit product");
+    return (mix >> LZ_CHECK_LO & 0x7Fu) << 17;
+}
 
 // Offset of visit v from the run start and the step taken after it, closed form of
 // "step = searchMatchNb++ >> Lizard_skipTrigger" (reference lizard_parser_fast.h:75-82):
@@ -188,6 +201,19 @@ LZ_DEV void lz_count_both(const u8* src, u32 P, u32 M, u32 limit, u32 anchor, u3
     else back = 64u + lz_count_back(src, P - 64u, M - 64u, anchor);
 }
 
+// Marks of the count trips behind a winner and of the check bits (lz_parse_fast, LANEFORMS).  The 64 LZ_STAT numbers are all but taken,
+// and two of these marks count lanes, not events, so they have counters of their own like LZ_HC_MARK: tests/emul/count_trip_api.cpp
+// defines LZ_CT_MARK(i, n) (add n to counter i, once per wave) before it includes this file; everywhere else the marks are empty and
+// what only feeds one is dead code.
+//   (0..2 were the joint trip's, measured and taken out)      3 back trip taken behind the next-run request      4 candidate lanes whose 4-byte test fails      5 rounds without a winner that
+//   issued a batch      6 eligible probes (age and lowPos rule pass) whose four bytes differ      7 rounds without a winner
+//   8 forward trip alone      9 back trip alone, in the parent's place
+#ifndef LZ_CT_MARK
+#define LZ_CT_MARK(i, n) ((void)0)
+#define LZ_CT_MARKS 0
+#else
+#define LZ_CT_MARKS 1
+#endif
 // Wave-wide byte copy (all lanes call; n uniform). dst/src need no alignment.
 LZ_DEV void lz_copy(u8* dst, const u8* src, u32 n)
 {
@@ -424,7 +450,7 @@ struct LzTab {
         oa = ((al >> sla) & 0xFFFFu) | (((ah >> sha) & 0xFFu) << 16);
         ob = ((bl >> slb) & 0xFFFFu) | (((bh >> shb) & 0xFFu) << 16);
     }
-    LZ_DEVM u32  entry(u32 p, u32 first4) const { return (p & 0x1FFFFu) | (lz_check_mix(first4) >> 25 << 17); }
+    LZ_DEVM u32  entry(u32 p, u32 first4) const { return (p & 0x1FFFFu) | lz_check7(lz_check_mix(first4)); }
     LZ_DEVM u32  get(u32 h) const { return (u32)lo[h] | ((u32)hi[h] << 16); }
     LZ_DEVM u32  get(u32 h, u32) const { return get(h); }
     LZ_DEVM void set(u32 h, u32 ent) const { lo[h] = (u16)ent; hi[h] = (u8)(ent >> 16); }
@@ -699,6 +725,17 @@ LZ_DEV u32 lz_back_lane(u32 c, u32 r)
 #ifndef LZ_LATCH_CHAIN
 #define LZ_LATCH_CHAIN 1
 #endif
+// The count trips behind a winner of the LANEFORMS round whose batch left a length unresolved (profiles/count_trip_ab.txt):
+//   LZ_BACK_LATE    the backward length unresolved: its trip behind the request for the next run's bytes (only the push needs it; the
+//                   forward trip, where there is one, keeps its place).  +1.2 % alone, +0.6 % beside the check field (LZ_CHECK_LO).
+// Measured with it and taken out (same file): both lengths unresolved counted in ONE trip, the forward pair (64 lanes x 8 bytes from
+// P + 4 / M + 4) and the backward pair (the bytes at P - 1 - lane / M - 1 - lane) requested before the first wait — +0.6 % alone,
+// nothing beside the check field, -0.6 % beside the late back trip, which already takes the second trip of such a pair off the way
+// to the next round.
+// Forward alone, or neither: the order of instructions is unchanged.  Every other instantiation keeps the two calls in a row.
+#ifndef LZ_BACK_LATE
+#define LZ_BACK_LATE 1
+#endif
 // LZ_STAT(8..12) below count paths for the test emulator (tests/emul); on the device LZ_STAT is empty and what only feeds a mark
 // (`nch`, the second test behind a stale stop, the fourth-round test) is dead code — marked "emulator only" where it stands.
 // LANEFORMS (the level-10 producers): the chain loop's dead set kept per reader and the slot schedule as a recurrence, both below.
@@ -721,6 +758,7 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
     // lane 0.)  Where inside that slack a sweep runs changes no decision: a slot older than 65535 is dead for the reference either way.
     constexpr bool kSweepMoved = LANEFORMS && TAB::kSweeps && LZ_TAIL_SWEEP;
     constexpr bool kBackLane = kLaneChain && LZ_LATCH_CHAIN;          // the chain pass on lane-prepared lengths, exits folded
+    constexpr bool kBackLate = LANEFORMS && LZ_BACK_LATE;             // the back trip: behind the next run's request
     // Source read-ahead (lz_touch.h): behind its table exchange every round asks, through the scalar path, for the source lines up to
     // LZ_READAHEAD in front of its first position, LZ_RA_PER_ROUND of them at most, and consumes what the round before asked for —
     // the exchange's own lgkmcnt(0) has covered those, and the new ones have a whole round until the next one.  (Asked for at the HEAD
@@ -882,6 +920,15 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
         lz_pin(fwd); lz_pin(cbk);                                    // computed here, under this batch's counted wait
         const u64 okMask = lz_ballot(ok);                              // uniform
         const u64 validMask = lz_ballot(valid);                        // uniform, a prefix of lanes
+        if constexpr (LZ_CT_MARKS != 0) {                              // emulator only: what the check bits let through (LZ_CT_MARK 4..7)
+            const u64 candMask = lz_ballot(cand);
+            const bool eligible = valid && !putOnly && age >= LZ_MIN_OFFSET && age <= LZ_MAX_DIST_LZ4 && age <= p - lowPos;
+            const u64 differ = lz_ballot(eligible && lz_ld32(src + (eligible ? ep : S)) != first4);
+            (void)candMask; (void)differ;                              // (the marks' arguments are evaluated by one lane: ballots stay outside)
+            LZ_CT_MARK(4, lz_popc64(candMask & ~okMask));
+            LZ_CT_MARK(6, lz_popc64(differ));
+            if (!okMask) { LZ_CT_MARK(7, 1u); if (candMask) LZ_CT_MARK(5, 1u); }
+        }
         u32 w = 0;
         u64 commit = validMask;
         u64 deadMask = 0;                                            // lanes inside the matches of chained sequences
@@ -985,11 +1032,22 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
         // (profile builds, level-10 producers) the count trips apart from the rest of the extension: slot 4 their clocks, slot 14 how
         // many were taken, slot 12 the rounds with a winner — trips per round and clocks per trip in profiles/source_readahead_ab.txt
         if constexpr (LANEFORMS) { LZ_PROF(st, 2); st.prof[12]++; if (ml == 0xFFFFu) st.prof[14]++; if (back == 0xFFFFu) st.prof[14]++; }
+        // the trips by kind (profiles/count_trip_ab.txt): slot 4 the forward trips alone, 8 the back trips alone, 9 the first and 10 the
+        // second trip of a pair; slot 11 counts the back-alone winners in its low half and the pairs in its high half
+        const u32 profKind = (ml == 0xFFFFu ? 1u : 0u) | (back == 0xFFFFu ? 2u : 0u);
+        if constexpr (LANEFORMS) st.prof[11] += profKind == 2u ? 1ull : profKind == 3u ? 1ull << 32 : 0ull;
 #endif
-        if (ml == 0xFFFFu) ml = 4u + lz_count_fwd(src, P + 4u, M + 4u, matchlimit);            // fast.h:100
-        if (back == 0xFFFFu) back = lz_count_back(src, P, M, anchor);                           // fast.h:102
+        bool backLate = false;                                           // uniform: the back trip waits until the next run's bytes are asked for
+        if (ml == 0xFFFFu) { LZ_CT_MARK(8, 1u); ml = 4u + lz_count_fwd(src, P + 4u, M + 4u, matchlimit); }    // fast.h:100
 #ifdef LZ_PROFILE
-        if constexpr (LANEFORMS) LZ_PROF(st, 4);
+        if constexpr (LANEFORMS) LZ_PROF(st, profKind == 3u ? 9 : 4);
+#endif
+        if (back == 0xFFFFu) {
+            if constexpr (kBackLate) { backLate = true; back = 0u; }
+            else { LZ_CT_MARK(9, 1u); back = lz_count_back(src, P, M, anchor); }            // fast.h:102
+        }
+#ifdef LZ_PROFILE
+        if constexpr (LANEFORMS) if (profKind >= 2u && !backLate) LZ_PROF(st, profKind == 3u ? 10 : 8);
 #endif
         if constexpr (TAB::kSweeps) {
             // A match moves ip by up to a sub-block at once (128 KiB - 1), four sweep intervals of the 17-bit table, and the round's
@@ -1015,6 +1073,20 @@ LZ_DEV void lz_parse_fast(const u8* src, u32 S, u32 E, const TAB& table, LzStrea
         if constexpr (kNarrow) { W = kW0; validNext = validNext && lane < kW0; }
         if (ip > mflimit) validNext = false;                             // (fast.h:143: there is no next run; any readable address)
         nextBytes = lz_ld64(src + (validNext ? pNext : S));
+        if constexpr (kBackLate) if (backLate) {
+            // The backward length was unresolved.  It is not on the way to the next round: ip = P + ml is the same before and
+            // after P -= back, ml += back, and the make-up sweeps above go by the forward length.  Only the push needs it, so its
+            // trip stands here, behind the request for the next run's bytes and no longer in front of it.
+            LZ_CT_MARK(3, 1u);
+#ifdef LZ_PROFILE
+            LZ_PROF(st, 2);
+#endif
+            back = lz_count_back(src, P, M, anchor);                     // fast.h:102
+            P -= back; M -= back; ml += back;
+#ifdef LZ_PROFILE
+            LZ_PROF(st, profKind == 3u ? 10 : 8);
+#endif
+        }
         push(P - anchor, ml, P - M);                                     // fast.h:138 (encoded later, in parallel)
         anchor = ip;
         if (ip > mflimit) break;                                         // fast.h:143
