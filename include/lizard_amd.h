@@ -689,6 +689,110 @@ int LizardGPU_streamIndex_device(const void* d_src, size_t srcSize, uint64_t* fr
  * of LizardGPU_framesDecodeDeviceStats), [3] stream-walk segments launched.  0 or -LIZARDGPU_ERR_*. */
 int LizardGPU_streamDecodeDeviceStats(unsigned long long out[4]);
 
+/* ---- SEEKABLE streams: a table of every item's place in a skippable frame at the END of the stream ----
+ * Nothing in a stream says where frame k starts, so LizardGPU_decompressStream_device follows the chain with one wave, and a caller who
+ * wants three items of a thousand decodes all of them.  A seekable stream ends in a SEEK TABLE (the idea of zstd's seekable format):
+ * a skippable frame that every decoder of the format steps over — the reference's CLI folds the magic numbers 0x184D2A50 .. 5F into
+ * "skippable" (programs/lizardio.c) — and from which a reader that knows it takes every item's place out of the stream's last bytes.
+ * Opt-in on both sides: no entry above changes its bytes, its launches or its waits.
+ *
+ * The format, all fields little-endian; the table frame is the LAST thing in the stream:
+ *     u32  0x184D2A5E (LIZARDGPU_SEEK_MAGIC)      skippable magic (tensor headers use ...54)
+ *     u32  24 * n + 16                            bytes that follow
+ *     n x  { u64 offset; u64 decodedBytes; u32 prefixBytes; u32 flags = 0 }        LizardGPU_seekEntry_t, 24 bytes
+ *     u64  n     u32 version = 1     u32 0x4B535A4C ("LZSK", LIZARDGPU_SEEK_TAG)    the footer: the stream's last 16 bytes
+ * Entry i describes ITEM i of the writing call: an opaque prefix of prefixBytes bytes (a tensor stream's tensor header; may be empty)
+ * at `offset`, then one frame that decodes to decodedBytes bytes.  Item i ends where item i + 1 starts, the last item where the table
+ * frame starts.  A table is USABLE for a stream of S bytes when the tag and the version match, the size field is 24 n + 16 and the
+ * table frame is exactly the last 24 n + 24 bytes of the stream (tableOffset = S - (24 n + 24)), n >= 1, entry 0 starts at 0,
+ * offset[i] + prefixBytes[i] < offset[i + 1] <= tableOffset (offset[n] standing for tableOffset), all flags are 0 and the sum of
+ * decodedBytes does not wrap.  Anything else is "no usable table"; it is never an error of the stream, whose frames decode as before.
+ * The CONCATENATION of two seekable streams is a valid stream whose table does not describe it, and these rules ALONE cannot say so:
+ * the last table's offsets count from the second stream's start, and its last item "ends" where the table starts, so the rules
+ * hold with a last item that swallows everything in between.  The decoder is what notices (below: the table locates, the decoder
+ * validates): that item's frame does not fill its region, so LizardGPU_decompressSeekableStream_device falls back to the walk and
+ * answers for the whole concatenation, and LizardGPU_decompressStreamItems_device refuses that item; the earlier indices name bytes
+ * of the FIRST stream there.  Do not read items out of a concatenation; write one table over all items instead.
+ * Out of scope: places INSIDE a frame (block-level tables) and element ranges inside a tensor.
+ *
+ * The host codec (lizard_seek_host.c; no device, no HIP):
+ * LizardGPU_seekTableBytes(n): 24 n + 24, the bytes of the table frame for n items, or a code LizardGPU_frameIsError recognises
+ * (GENERIC) when 24 n + 16 does not fit the u32 size field.
+ * LizardGPU_seekTableWrite: the table frame for entries[0 .. n) into dst; the bytes written, or 0 (a null pointer, n == 0, no room in
+ * dstCapacity, a size that does not fit).  It writes the entries as they are: whether a reader finds them usable is the caller's affair.
+ * LizardGPU_seekTableRead judges the table from the LAST tailBytes bytes of a stream of streamBytes bytes (tail[0] is byte
+ * streamBytes - tailBytes of the stream) and reads nothing outside tail[0 .. tailBytes):
+ *   LIZARDGPU_SEEK_USABLE   *n items, the table frame starts at *tableOffset, the first min(*n, maxEntries) entries are in `entries`
+ *                           (may be NULL with maxEntries 0): a caller whose array was too short sees *n > maxEntries and calls again.
+ *   LIZARDGPU_SEEK_NONE     the stream does not end in the footer's tag (or is shorter than the shortest table frame, 48 bytes).
+ *   LIZARDGPU_SEEK_MORE     the footer is there and its n plausible, but the tail is too short to judge the table: call again with
+ *                           at least LizardGPU_seekTableBytes(*n) bytes of tail.  (A tail shorter than the 16-byte footer of a stream
+ *                           of 48 bytes or more: *n = 0, i.e. "at least 24 bytes".)
+ *   LIZARDGPU_SEEK_DAMAGED  the tag is there and a rule above fails.  The entries written so far are unspecified.
+ * NONE and DAMAGED both mean "no usable table"; -LIZARDGPU_ERR_ARG for a null tail / n / tableOffset or tailBytes > streamBytes. */
+typedef struct { uint64_t offset; uint64_t decodedBytes; uint32_t prefixBytes; uint32_t flags; } LizardGPU_seekEntry_t;
+#define LIZARDGPU_SEEK_MAGIC   0x184D2A5Eu
+#define LIZARDGPU_SEEK_TAG     0x4B535A4Cu
+#define LIZARDGPU_SEEK_VERSION 1u
+#define LIZARDGPU_SEEK_USABLE  0
+#define LIZARDGPU_SEEK_NONE    1
+#define LIZARDGPU_SEEK_MORE    2
+#define LIZARDGPU_SEEK_DAMAGED 3
+size_t LizardGPU_seekTableBytes(size_t n);
+size_t LizardGPU_seekTableWrite(void* dst, size_t dstCapacity, const LizardGPU_seekEntry_t* entries, size_t n);
+int    LizardGPU_seekTableRead(const void* tail, size_t tailBytes, uint64_t streamBytes, LizardGPU_seekEntry_t* entries, size_t maxEntries,
+                               size_t* n, uint64_t* tableOffset);
+
+/* The writer: LizardGPU_compressStream_device (Part 3) with the table behind it.  Same arguments, same refusals in the same order,
+ * and d_dst[0 .. frameOffsets[nFrames]) is byte for byte that entry's stream for the same arguments; behind it the table frame of
+ * LizardGPU_seekTableWrite over { frameOffsets[i], srcSizes[i], prefixSizes[i], 0 }.  The return value is the whole size,
+ * frameOffsets[nFrames] (when asked for) where the TABLE starts, i.e. the plain entry's return value.
+ * LizardGPU_compressStreamBound + LizardGPU_seekTableBytes(nFrames) bytes always suffice; dstMaxSize_tooSmall and "nothing outside
+ * d_dst[0 .. dstCapacity) is written" hold as there.  Additionally GENERIC, before anything is launched, for a prefix of 2^32 bytes or
+ * more or a table whose size field would not fit.  The host still waits ONCE: the table's bytes join the bytes the host knows, so
+ * the device's one capacity test covers them, and one more kernel (lz_stream_seektable_kernel, one thread per entry) writes the table
+ * behind the kernel that settles the frame offsets — nothing at all after an overflow.  Counted in LizardGPU_streamCompressDeviceStats. */
+size_t LizardGPU_compressSeekableStream_device(void* d_dst, size_t dstCapacity, size_t nFrames, const void* const* d_srcs, const size_t* srcSizes,
+                                               const void* const* prefixes, const size_t* prefixSizes, const LizardGPU_framePrefs_t* prefs,
+                                               uint64_t* frameOffsets, size_t* failedFrame, void* stream);
+
+/* The table of the stream at d_src (device memory): the footer comes down, then the table frame (two small copies, two waits, ordered
+ * after what `stream` holds), and LizardGPU_seekTableRead judges it.  LIZARDGPU_SEEK_USABLE with *n, *tableOffset and the first
+ * min(*n, maxEntries) entries as there, LIZARDGPU_SEEK_NONE or LIZARDGPU_SEEK_DAMAGED (never _MORE); a stream under 48 bytes is NONE
+ * without a copy.  -LIZARDGPU_ERR_* for a null pointer or when the machinery fails. */
+int LizardGPU_seekTable_device(const void* d_src, size_t srcSize, LizardGPU_seekEntry_t* entries, size_t maxEntries, size_t* n,
+                               uint64_t* tableOffset, void* stream);
+
+/* LizardGPU_decompressStream_device without the serial walk.  Signature and CONTRACT are that entry's: for every input — return value,
+ * consumed bytes, frame count, decoded count, decoded bytes — the answer is what LizardGPU_decompressStream_device answers.
+ * Fast path, when the table is usable and the sum of decodedBytes fits dstCapacity: ONE call of LizardGPU_decompressFrames_device over
+ * all items, each item's frame with decodedBytes as its capacity at its packed place, each non-empty prefix as a frame of capacity
+ * 0 (a skippable frame decodes to nothing).  It stands only if every frame answers EXACTLY its entry: result = decodedBytes (0 for a
+ * prefix), consumed = its whole region.  The answer is then the sum, srcSize, and the batch's frames + 1 (the table frame).
+ * On ANY deviation — no usable table, a sum above dstCapacity, one frame answering otherwise, a failure of the batch —
+ * LizardGPU_decompressStream_device runs from the start and its answer is returned: the table locates, it never decides an answer. */
+size_t LizardGPU_decompressSeekableStream_device(void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize, size_t* srcConsumedPtr,
+                                                 size_t* nFramesPtr, size_t* decodedPtr, unsigned flags, void* stream);
+
+/* Only the listed items of a seekable stream, decoded back to back into d_dst: items[0 .. nItems) are indices into the table,
+ * STRICTLY ASCENDING; itemOffsets (may be NULL, else nItems + 1 host entries): where item items[k] starts in d_dst, and the total.
+ * Returns the total or a code LizardGPU_frameIsError recognises.  The table locates, the decoder validates: every listed item's frame
+ * (not its prefix, which is not read) goes through ONE LizardGPU_decompressFrames_device with decodedBytes as its capacity.
+ *   - frameType_unknown: the stream has no usable table (nothing is decoded: use LizardGPU_decompressStream_device);
+ *   - frameSize_wrong: items[k] >= the table's n; blockMode_invalid: items[k] <= items[k - 1]; *failedItem (may be NULL) = k for both,
+ *     nothing is decoded;
+ *   - dstMaxSize_tooSmall: the listed items' decodedBytes exceed dstCapacity, nothing is decoded;
+ *   - an item whose frame does not answer exactly its entry: the frame's own error code, or decompressionFailed when it decoded to
+ *     another size or did not fill its region; *failedItem = k of the first such item; what d_dst holds of other items is valid;
+ *   - GENERIC for a null pointer or when the machinery fails.
+ * nItems == 0 returns 0 and touches nothing.  Synchronous, ordered after what `stream` holds. */
+size_t LizardGPU_decompressStreamItems_device(void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize, const size_t* items,
+                                              size_t nItems, uint64_t* itemOffsets, size_t* failedItem, unsigned flags, void* stream);
+
+/* Since process start, selected device: [0] LizardGPU_decompressSeekableStream_device calls answered through the table, [1] calls
+ * that fell back to the walk, [2] items decoded by LizardGPU_decompressStreamItems_device, [3] tables read from device memory. */
+int LizardGPU_seekDeviceStats(unsigned long long out[4]);
+
 /* =====================================================================================================
  * Part 3c — tensor streams: element bytes split into planes before they are compressed.
  *

@@ -138,6 +138,20 @@ def lib():
     L.LizardGPU_planesXorStats.argtypes = [c.c_void_p]; L.LizardGPU_planesXorStats.restype = c.c_int
     L.LizardGPU_tensorHeaderWrite3.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p]; L.LizardGPU_tensorHeaderWrite3.restype = c.c_size_t
     L.LizardGPU_tensorHeaderRead3.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]; L.LizardGPU_tensorHeaderRead3.restype = c.c_int
+    L.LizardGPU_seekTableBytes.argtypes = [c.c_size_t]; L.LizardGPU_seekTableBytes.restype = c.c_size_t
+    L.LizardGPU_seekTableWrite.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t]; L.LizardGPU_seekTableWrite.restype = c.c_size_t
+    L.LizardGPU_seekTableRead.argtypes = [c.c_void_p, c.c_size_t, c.c_uint64, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
+    L.LizardGPU_seekTableRead.restype = c.c_int
+    L.LizardGPU_compressSeekableStream_device.argtypes = L.LizardGPU_compressStream_device.argtypes
+    L.LizardGPU_compressSeekableStream_device.restype = c.c_size_t
+    L.LizardGPU_seekTable_device.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p]
+    L.LizardGPU_seekTable_device.restype = c.c_int
+    L.LizardGPU_decompressSeekableStream_device.argtypes = L.LizardGPU_decompressStream_device.argtypes
+    L.LizardGPU_decompressSeekableStream_device.restype = c.c_size_t
+    L.LizardGPU_decompressStreamItems_device.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p,
+                                                         c.c_uint, c.c_void_p]
+    L.LizardGPU_decompressStreamItems_device.restype = c.c_size_t
+    L.LizardGPU_seekDeviceStats.argtypes = [c.c_void_p]; L.LizardGPU_seekDeviceStats.restype = c.c_int
     _lib = L
     return L
 

@@ -413,7 +413,8 @@ def decompress_frames_device(frames, sizes=None, verify_checksum=True):
 STREAM_FRAME_SLACK = 8          # bytes compress_stream_device gives every frame beyond LizardGPU_compressFrameBound (5 are needed)
 
 
-def compress_stream_device_into(tensors, dst=None, prefixes=None, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksum=False, content_size=True):
+def compress_stream_device_into(tensors, dst=None, prefixes=None, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksum=False, content_size=True,
+                                seekable=False):
     """A .liz STREAM for `tensors` — contiguous uint8 CUDA tensors on one device, zero-length ones allowed — written into ONE uint8 CUDA
     tensor in ONE call of LizardGPU_compressStream_device on torch's current stream: per tensor `prefixes[i]` (host bytes, opaque to
     the entry; None: no prefixes) and then the frame compress_frame_device writes for tensor i with 8 bytes more than its
@@ -421,7 +422,10 @@ def compress_stream_device_into(tensors, dst=None, prefixes=None, level=LIZARD_M
     place, and no payload byte crosses PCIe, with or without `checksum`.  Without `dst` the output has
     LizardGPU_compressStreamBound bytes — the only allocation of the call; a `dst` that is too small raises (dstMaxSize_tooSmall),
     as does a tensor the single-frame entry would refuse, naming the first such tensor.  Returns (dst[:n], offsets): the stream, and
-    the n + 1 places where prefix 0, prefix 1, ... start and the stream ends."""
+    the n + 1 places where prefix 0, prefix 1, ... start and the stream ends.
+    seekable=True (opt-in; without it the call is what it was): LizardGPU_compressSeekableStream_device — the same bytes, and behind
+    them a seek table (a skippable frame, include/lizard_amd.h Part 3b) written by one more kernel of the same call; offsets[n] is
+    then where the TABLE starts, and `dst` needs LizardGPU_seekTableBytes(n) bytes more."""
     import torch
     L = _lib.lib()
     tensors = list(tensors)
@@ -452,16 +456,18 @@ def compress_stream_device_into(tensors, dst=None, prefixes=None, level=LIZARD_M
         pre_ptrs = (ctypes.c_void_p * n)(*ptrs)
     if dst is None:
         cap = _lib.check_frame(L.LizardGPU_compressStreamBound(n, sizes, pre_sizes, ctypes.byref(p)), "LizardGPU_compressStreamBound")
+        if seekable:
+            cap += _lib.check_frame(L.LizardGPU_seekTableBytes(n), "LizardGPU_seekTableBytes")
         dst = torch.empty(cap, dtype=torch.uint8, device=device)
     assert dst.is_cuda and dst.dtype == torch.uint8 and dst.is_contiguous() and dst.device == device
     offsets = (ctypes.c_uint64 * (n + 1))()
     failed = ctypes.c_size_t(0)
     L.LizardGPU_setDevice(device.index or 0)
     stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    r = L.LizardGPU_compressStream_device(dst.data_ptr(), int(dst.numel()), n, srcs, sizes, pre_ptrs, pre_sizes, ctypes.byref(p), offsets,
-                                          ctypes.byref(failed), stream)
+    name = "LizardGPU_compressSeekableStream_device" if seekable else "LizardGPU_compressStream_device"
+    r = getattr(L, name)(dst.data_ptr(), int(dst.numel()), n, srcs, sizes, pre_ptrs, pre_sizes, ctypes.byref(p), offsets, ctypes.byref(failed), stream)
     if L.LizardGPU_frameIsError(r):
-        raise _lib.LizardAmdError(f"LizardGPU_compressStream_device: {L.LizardF_getErrorName(r).decode()} "
+        raise _lib.LizardAmdError(f"{name}: {L.LizardF_getErrorName(r).decode()} "
                                   f"{L.LizardGPU_lastError().decode(errors='replace')}".strip())
     return dst[:r], [int(o) for o in offsets]
 
@@ -477,7 +483,7 @@ def _compress_stream_device_cat(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=
     return torch.cat(frames)
 
 
-def compress_stream_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksum=False):
+def compress_stream_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksum=False, seekable=False):
     """A .liz STREAM for `tensors`: one frame with content size per tensor, back to back, in ONE call of
     LizardGPU_compressStream_device (compress_stream_device_into without prefixes) into ONE allocation of
     LizardGPU_compressStreamBound bytes.  Returns one uint8 CUDA tensor, a view of that allocation: the frames, which the
@@ -486,11 +492,46 @@ def compress_stream_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, ch
     Every frame gets STREAM_FRAME_SLACK = 8 bytes of room more than LizardGPU_compressFrameBound (see the note at that function in
     include/lizard_amd.h; the stream bound counts them): a block of ONE byte makes a record with 6 bytes of payload,
     5 more than the bound counts.  The 8 bytes a header without content size leaves unused hide that; a 15-byte header does not, so
-    with the bound alone a tensor of one byte — or one whose size is one more than a multiple of the block size — is refused."""
+    with the bound alone a tensor of one byte — or one whose size is one more than a multiple of the block size — is refused.
+    seekable=True: the same frames with a seek table behind them (compress_stream_device_into), which decompress_stream_device(seek=True)
+    decodes without the serial walk over the frames."""
     tensors = list(tensors)
     if not tensors:
         raise ValueError("compress_stream_device: no tensors")
-    return compress_stream_device_into(tensors, None, None, level, block_size_id, checksum, True)[0]
+    return compress_stream_device_into(tensors, None, None, level, block_size_id, checksum, True, seekable)[0]
+
+
+class _SeekEntry(ctypes.Structure):
+    """LizardGPU_seekEntry_t"""
+    _fields_ = [("offset", ctypes.c_uint64), ("decodedBytes", ctypes.c_uint64), ("prefixBytes", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+SEEK_USABLE, SEEK_NONE, SEEK_MORE, SEEK_DAMAGED = 0, 1, 2, 3      # LIZARDGPU_SEEK_*
+
+
+def stream_seek_table_device(src):
+    """LizardGPU_seekTable_device: the seek table at the end of the stream in `src`, a contiguous uint8 CUDA tensor — two small copies
+    from its last bytes on torch's current stream, no walk.  One dict per item of the writing call: "offset" (where its prefix starts),
+    "prefix_bytes", "frame_bytes" (of the frame behind the prefix) and "decoded_bytes"; or None when the stream has no usable table
+    (none at all, or a damaged one: the stream's frames decode as ever)."""
+    import torch
+    L = _lib.lib()
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+    L.LizardGPU_setDevice(src.device.index or 0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
+    room = 1024
+    while True:
+        entries, n, at = (_SeekEntry * room)(), ctypes.c_size_t(0), ctypes.c_uint64(0)
+        rc = _lib.check(L.LizardGPU_seekTable_device(src.data_ptr(), int(src.numel()), entries, room, ctypes.byref(n), ctypes.byref(at), stream),
+                        "LizardGPU_seekTable_device")
+        if rc != SEEK_USABLE:
+            return None
+        if n.value <= room:
+            break
+        room = n.value
+    ends = [int(e.offset) for e in entries[1:n.value]] + [int(at.value)]
+    return [{"offset": int(e.offset), "prefix_bytes": int(e.prefixBytes), "frame_bytes": end - int(e.offset) - int(e.prefixBytes),
+             "decoded_bytes": int(e.decodedBytes)} for e, end in zip(entries[:n.value], ends)]
 
 
 def stream_info_device(src):
@@ -521,17 +562,23 @@ def stream_info_device(src):
             for f, k, b, o in zip(infos[:n.value], nrec[:n.value], fbytes[:n.value], offs[:n.value])]
 
 
-def decompress_stream_device(src, dst=None, size=None, verify_checksum=True):
+def decompress_stream_device(src, dst=None, size=None, verify_checksum=True, seek=False):
     """Decode the stream of frames in `src`, a contiguous uint8 CUDA tensor, into one uint8 CUDA tensor on the same device
     (LizardGPU_decompressStream_device) on torch's current stream: the frames are found on the device and decoded in batches, a stream
     whose frames carry their content size (compress_stream_device) in ONE batch; neither the frames nor the decoded bytes cross PCIe.
     Without `dst` the output has `size` bytes, or, without `size`, what one stream_info_device call promises: per frame the content
     size, else n_records times the frame's block size (an upper bound).  Returns (dst_view, n_frames): the decoded bytes of all
-    frames joined, and how many frames there were.  An error code raises LizardAmdError naming the offset of the refused frame."""
+    frames joined, and how many frames there were.  An error code raises LizardAmdError naming the offset of the refused frame.
+    seek=True: LizardGPU_decompressSeekableStream_device — the same answer for every stream; one that ends in a usable seek table
+    (compress_stream_device(..., seekable=True)) is decoded from the table's places in one batch without the walk, and without
+    `dst` and `size` the table gives the size; any other stream takes the path above."""
     import torch
     L = _lib.lib()
     assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
     if dst is None:
+        if size is None and seek:
+            table = stream_seek_table_device(src)
+            size = None if table is None else sum(e["decoded_bytes"] for e in table)
         if size is None:
             size = sum(0 if f["skippable"] else f["content_size"] or f["n_records"] * L.LizardGPU_frameBlockSize(f["block_size_id"])
                        for f in stream_info_device(src))
@@ -540,12 +587,49 @@ def decompress_stream_device(src, dst=None, size=None, verify_checksum=True):
     L.LizardGPU_setDevice(src.device.index or 0)
     stream = ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
     used, frames, decoded = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
-    r = L.LizardGPU_decompressStream_device(dst.data_ptr(), int(dst.numel()), src.data_ptr(), int(src.numel()), ctypes.byref(used),
-                                            ctypes.byref(frames), ctypes.byref(decoded), 0 if verify_checksum else FRAME_SKIP_CHECKSUM, stream)
+    name = "LizardGPU_decompressSeekableStream_device" if seek else "LizardGPU_decompressStream_device"
+    r = getattr(L, name)(dst.data_ptr(), int(dst.numel()), src.data_ptr(), int(src.numel()), ctypes.byref(used), ctypes.byref(frames),
+                         ctypes.byref(decoded), 0 if verify_checksum else FRAME_SKIP_CHECKSUM, stream)
     if L.LizardGPU_frameIsError(r):
-        raise _lib.LizardAmdError(f"LizardGPU_decompressStream_device: frame {frames.value} at offset {used.value}: "
+        raise _lib.LizardAmdError(f"{name}: frame {frames.value} at offset {used.value}: "
                                   f"{L.LizardF_getErrorName(r).decode()} ({L.LizardGPU_lastError().decode()})")
     return dst[:r], frames.value
+
+
+def _decompress_stream_items_device(src, items, size, verify_checksum=True):
+    """LizardGPU_decompressStreamItems_device: the items `items` (strictly ascending indices into the seek table) of the seekable stream
+    in `src` decoded back to back into one new uint8 CUDA tensor of `size` bytes, on torch's current stream."""
+    import torch
+    L = _lib.lib()
+    n = len(items)
+    dst = torch.empty(max(int(size), 1), dtype=torch.uint8, device=src.device)[:int(size)]
+    L.LizardGPU_setDevice(src.device.index or 0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
+    failed = ctypes.c_size_t(0)
+    r = L.LizardGPU_decompressStreamItems_device(dst.data_ptr(), int(dst.numel()), src.data_ptr(), int(src.numel()), (ctypes.c_size_t * max(n, 1))(*items), n,
+                                                 None, ctypes.byref(failed), 0 if verify_checksum else FRAME_SKIP_CHECKSUM, stream)
+    if L.LizardGPU_frameIsError(r):
+        raise _lib.LizardAmdError(f"LizardGPU_decompressStreamItems_device: {L.LizardF_getErrorName(r).decode()} ({L.LizardGPU_lastError().decode()})")
+    return dst[:r]
+
+
+def decompress_stream_items_device(src, items, verify_checksum=True):
+    """Only the listed items of the seekable stream in `src` (a contiguous uint8 CUDA tensor): `items` are strictly ascending indices
+    into its seek table.  A list of uint8 CUDA views into one allocation, one per listed item.  Raises LizardAmdError for a stream
+    without a usable seek table, an index out of range or not ascending, and for an item whose frame does not answer its entry."""
+    import torch
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+    items = [int(k) for k in items]
+    if not items:
+        return []
+    table = stream_seek_table_device(src)
+    sizes = [table[k]["decoded_bytes"] if table is not None and 0 <= k < len(table) else 0 for k in items]
+    out = _decompress_stream_items_device(src, items, sum(sizes), verify_checksum)
+    views, at = [], 0
+    for n in sizes:
+        views.append(out[at:at + n])
+        at += n
+    return views
 
 
 # ---- tensor streams: element bytes split into planes before compressing (include/lizard_amd.h Part 3c) ----
@@ -701,7 +785,7 @@ def join_planes_xor_device(tensors, bases, elem_sizes, planes="bytes"):
 
 
 def compress_tensors_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, checksum=False, split=True, planes="bytes", base=None,
-                            base_tag=0):
+                            base_tag=0, seekable=False):
     """A .liz STREAM for `tensors`, contiguous CUDA tensors of any dtype and shape on one device (zero-element ones and scalars
     allowed), as ONE uint8 CUDA tensor: per tensor a tensor header — a skippable frame with the dtype's name, the shape and the
     element size of the split (LizardGPU_tensorHeaderWrite) — and one frame with content size over the tensor's bytes SPLIT INTO
@@ -733,7 +817,11 @@ def compress_tensors_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, c
     the path and the headers above.  Unchanged bits become zeros and the planes put them into runs: bf16 weights one Adam step of
     lr 1e-5 behind their base are 0.31 of raw at level 10 and 0.15 at level 30 (0.84 / 0.75 without).  Use it only against a base
     the data derives from: with an unrelated base it LOSES at level 10 with byte planes (0.91 against 0.84).  Readers of "LZT1" /
-    "LZT2" refuse "LZT3".  base with split=False raises ValueError."""
+    "LZT2" refuse "LZT3".  base with split=False raises ValueError.
+    seekable=True (opt-in; without it the bytes are what they were): the same stream with a seek table behind the last tensor
+    (compress_stream_device_into), one entry per tensor with the tensor header as its prefix.  decompress_tensors_device(seek=True)
+    then finds headers and frames without a walk, and select=[...] decodes some tensors only; readers that do not know the table
+    step over it."""
     L = _lib.lib()
     if planes not in ("bytes", "bits"):
         raise ValueError(f"compress_tensors_device: planes={planes!r} is neither 'bytes' nor 'bits'")
@@ -784,15 +872,45 @@ def compress_tensors_device(tensors, level=LIZARD_MIN_CLEVEL, block_size_id=0, c
             raise _lib.LizardAmdError(f"compress_tensors_device: tensor {i}: LizardGPU_tensorHeaderWrite3 refused the descriptor")
         headers.append(host[at:at + n].tobytes())
         at += n
-    return compress_stream_device_into(raw, None, headers, level, block_size_id, checksum, True)[0]
+    return compress_stream_device_into(raw, None, headers, level, block_size_id, checksum, True, seekable)[0]
 
 
-def _tensor_stream_index(src, what):
-    """The (tensor header, data frame) pairs of the tensor stream in `src`: one stream_info_device, one indexed read of all header
-    bytes.  [(header frame, data frame, descriptor)]."""
-    import torch
-    L = _lib.lib()
+SEEK_MAGIC = 0x184D2A5E                     # LIZARDGPU_SEEK_MAGIC: the skippable frame that holds a seek table
+
+
+def _tensor_stream_pairs_seek(src, what, select):
+    """The (tensor header, data frame) pairs from the stream's seek table, in the keys of stream_info_device that the tensor entries use;
+    with `select` those tensors only.  (pairs, tensors in the stream)"""
+    table = stream_seek_table_device(src)
+    if table is None:
+        raise _lib.LizardAmdError(f"{what}: the stream has no usable seek table (write it with seekable=True, or read it without seek / select)")
+    picked = range(len(table)) if select is None else select
+    pairs = []
+    for j, k in enumerate(picked):
+        if not 0 <= k < len(table):
+            raise _lib.LizardAmdError(f"{what}: select[{j}] = {k}, the stream has {len(table)} tensors")
+        if j and k <= picked[j - 1]:
+            raise _lib.LizardAmdError(f"{what}: select[{j}] = {k} does not ascend from select[{j - 1}] = {picked[j - 1]}")
+        e = table[k]
+        if not e["prefix_bytes"]:
+            raise _lib.LizardAmdError(f"{what}: tensor {k}: the data frame at offset {e['offset']} has no tensor header in front of it")
+        pairs.append(({"offset": e["offset"], "frame_bytes": e["prefix_bytes"]},
+                      {"offset": e["offset"] + e["prefix_bytes"], "frame_bytes": e["frame_bytes"], "content_size": e["decoded_bytes"],
+                       "n_records": 1 if e["decoded_bytes"] else 0}))
+    return pairs, len(table)
+
+
+def _tensor_stream_index(src, what, seek=False, select=None):
+    """The (tensor header, data frame) pairs of the tensor stream in `src`: one stream_info_device — with `seek` the stream's seek
+    table instead, and no walk —, one indexed read of all header bytes.  ([(header frame, data frame, descriptor)], tensors in the
+    stream): with `select` (ascending indices; implies seek) the list holds those tensors only."""
+    if seek or select is not None:
+        pairs, count = _tensor_stream_pairs_seek(src, what, select)
+        return _tensor_stream_headers(src, what, pairs, range(count) if select is None else select), count
     frames = stream_info_device(src)
+    if len(frames) % 2 and frames[-1]["skippable"] and frames[-1]["frame_bytes"] >= 48 \
+            and int.from_bytes(bytes(src[frames[-1]["offset"]:frames[-1]["offset"] + 4].cpu().numpy()), "little") == SEEK_MAGIC:
+        frames.pop()                                           # a seekable stream read by the walk: its table is not a tensor
     pairs, i = [], 0
     while i < len(frames):
         k, f = len(pairs), frames[i]
@@ -802,13 +920,20 @@ def _tensor_stream_index(src, what):
             raise _lib.LizardAmdError(f"{what}: tensor {k}: the skippable frame at offset {f['offset']} is not followed by a data frame")
         pairs.append((f, frames[i + 1]))
         i += 2
+    return _tensor_stream_headers(src, what, pairs, range(len(pairs))), len(pairs)
+
+
+def _tensor_stream_headers(src, what, pairs, numbers):
+    """The descriptors of the tensor headers in front of `pairs`, tensors `numbers` of the stream: one indexed read of all header bytes."""
+    import torch
+    L = _lib.lib()
     if not pairs:
         return []
     takes = [min(h["frame_bytes"], TENSOR_HEADER3_MAX) for h, _ in pairs]
     index = np.concatenate([np.arange(h["offset"], h["offset"] + n, dtype=np.int64) for (h, _), n in zip(pairs, takes)])
     host = np.ascontiguousarray(src[torch.from_numpy(index).to(src.device)].cpu().numpy())
     out, at = [], 0
-    for k, ((h, f), n) in enumerate(zip(pairs, takes)):
+    for k, (h, f), n in zip(numbers, pairs, takes):
         d, used = _TensorDesc3(), ctypes.c_size_t(0)
         rc = L.LizardGPU_tensorHeaderRead3(host.ctypes.data + at, n, ctypes.byref(d), ctypes.byref(used))
         if rc or used.value != h["frame_bytes"]:
@@ -819,20 +944,22 @@ def _tensor_stream_index(src, what):
     return out
 
 
-def tensors_info_device(stream):
+def tensors_info_device(stream, seek=False):
     """What the tensor stream in `stream` (a contiguous uint8 CUDA tensor, what compress_tensors_device returns) holds, without
     decoding anything: one dict per tensor with dtype (its name), shape, planes ("bytes" or "bits": the filter), elem_size (of the
     split; with "bytes", 1 = stored unsplit), nbytes, offset (of the tensor's header in the stream), header_bytes and frame_bytes (of the data frame behind the header),
     xor_base (bool: an "LZT3" header — the tensor was XORed with a base, which decompress_tensors_device needs) and base_tag (the
     number the writer stored for that base; 0 without one).  Raises
-    LizardAmdError naming the tensor's index for a data frame without a tensor header in front of it."""
+    LizardAmdError naming the tensor's index for a data frame without a tensor header in front of it.  A seek table behind the last
+    tensor is not a tensor.  seek=True takes the places from the stream's seek table instead of a walk, and raises LizardAmdError
+    when the stream has no usable one."""
     return [{"dtype": d.dtype.decode(), "shape": tuple(int(s) for s in d.shape[:d.ndim]), "planes": _PLANES_NAMES[int(d.filter)],
              "elem_size": int(d.elemSize), "nbytes": int(d.nbytes), "xor_base": bool(d.flags & TENSOR_XOR_BASE), "base_tag": int(d.baseTag),
              "offset": h["offset"], "header_bytes": h["frame_bytes"], "frame_bytes": f["frame_bytes"]}
-            for h, f, d in _tensor_stream_index(stream, "tensors_info_device")]
+            for h, f, d in _tensor_stream_index(stream, "tensors_info_device", seek)[0]]
 
 
-def decompress_tensors_device(stream, verify_checksum=True, base=None, base_tag=None):
+def decompress_tensors_device(stream, verify_checksum=True, base=None, base_tag=None, seek=False, select=None):
     """The tensors of the tensor stream in `stream`, a contiguous uint8 CUDA tensor (what compress_tensors_device returns), with dtype
     and shape restored: a list of views into ONE allocation, each 256-byte aligned.  In this order: one stream_info_device, one
     indexed read of all header bytes, one decompress_stream_device — ONE decode batch for a stream of this library, because the headers
@@ -850,18 +977,25 @@ def decompress_tensors_device(stream, verify_checksum=True, base=None, base_tag=
     same result); a stream without one takes exactly the path above.  Raises LizardAmdError naming the tensor's index when an
     "LZT3" tensor has no base, when its base's byte size or dtype is not the header's, or when `base_tag` is given and differs
     from the header's.  A base handed for a tensor whose header is not "LZT3" is IGNORED.  The library cannot tell a wrong base
-    of the right size and tag: the tensor then comes back wrong, silently — the tag is the caller's guard."""
+    of the right size and tag: the tensor then comes back wrong, silently — the tag is the caller's guard.
+    A seekable stream (compress_tensors_device(..., seekable=True)) reads like any other here: the table behind the last tensor is
+    stepped over.  seek=True takes the places of headers and frames from that table — no stream_info_device, no walk in the decode
+    (decompress_stream_device(seek=True)) — and raises LizardAmdError when the stream has no usable one.  select=[indices] (strictly
+    ascending positions in the stream; implies seek) decodes ONLY those tensors, through LizardGPU_decompressStreamItems_device, and
+    returns them in that order; `base` stays indexed by position in the stream and as long as the stream has tensors."""
     import torch
     what = "decompress_tensors_device"
-    entries = _tensor_stream_index(stream, what)
+    select = None if select is None else [int(k) for k in select]
+    entries, count = _tensor_stream_index(stream, what, seek, select)
+    numbers = list(range(count)) if select is None else select
     if base is not None:
         base = list(base)
-        if len(base) != len(entries):
-            raise ValueError(f"{what}: {len(base)} bases for a stream of {len(entries)} tensors")
+        if len(base) != count:
+            raise ValueError(f"{what}: {len(base)} bases for a stream of {count} tensors")
     if not entries:
         return []
     dtypes = []
-    for k, (h, f, d) in enumerate(entries):
+    for k, (h, f, d) in zip(numbers, entries):
         known = f["content_size"] if f["n_records"] else 0
         if f["n_records"] and not f["content_size"]:
             raise _lib.LizardAmdError(f"{what}: tensor {k}: the data frame at offset {f['offset']} carries no content size")
@@ -886,7 +1020,10 @@ def decompress_tensors_device(stream, verify_checksum=True, base=None, base_tag=
             if not (b.is_cuda and b.is_contiguous() and b.device == stream.device):
                 raise _lib.LizardAmdError(f"{what}: tensor {k}: its base is not a contiguous CUDA tensor on {stream.device}")
     total = sum(int(d.nbytes) for _, _, d in entries)
-    decoded, _ = decompress_stream_device(stream, size=total, verify_checksum=verify_checksum)
+    if select is None:
+        decoded, _ = decompress_stream_device(stream, size=total, verify_checksum=verify_checksum, seek=seek)
+    else:
+        decoded = _decompress_stream_items_device(stream, select, total, verify_checksum)
     if int(decoded.numel()) != total:
         raise _lib.LizardAmdError(f"{what}: the stream decoded to {int(decoded.numel())} bytes, its headers say {total}")
     pieces, pos = [], 0
@@ -895,5 +1032,5 @@ def decompress_tensors_device(stream, verify_checksum=True, base=None, base_tag=
         pos += int(d.nbytes)
     xored = [bool(d.flags & TENSOR_XOR_BASE) for _, _, d in entries]
     joined = _planes_device(pieces, [int(d.elemSize) for _, _, d in entries], True, [int(d.filter) for _, _, d in entries],
-                            [_as_bytes(base[k]) if x else None for k, x in enumerate(xored)] if any(xored) else None, xored)
+                            [_as_bytes(base[k]) if x else None for k, x in zip(numbers, xored)] if any(xored) else None, xored)
     return [b.view(dt).reshape(tuple(int(s) for s in d.shape[:d.ndim])) for b, dt, (_, _, d) in zip(joined, dtypes, entries)]

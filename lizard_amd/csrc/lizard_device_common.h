@@ -35,6 +35,14 @@ size_t lzgpu_frame_write_header(uint8_t* dst, const LizardF_frameInfo_t* frameIn
 size_t lzgpu_frame_device_plan(LizardF_preferences_t* prefs, const LizardF_preferences_t* prefsPtr, const void* d_dst, size_t dstCapacity,
                                const void* d_src, size_t srcSize);
 
+/* lizard_stream_device.c: LizardGPU_compressStream_device with extraFixed bytes of room behind the last frame, which `after` (may be
+ * NULL) fills by enqueueing work on stream B behind lz_stream_finish_kernel (0 or -LIZARDGPU_ERR_*, which fails the call) */
+typedef int (*lzgpu_stream_after_fn)(void* arg, const LzFramesEntry* d_frames, const LzStreamEntry* d_entries, const LzStreamState* d_state,
+                                     const uint64_t* d_offsets, uint32_t nFrames, uint64_t fixedTotal, uint64_t capacity, hipStream_t B);
+size_t lzgpu_stream_compress(void* d_dst, size_t dstCapacity, size_t nFrames, const void* const* d_srcs, const size_t* srcSizes,
+                             const void* const* prefixes, const size_t* prefixSizes, const LizardGPU_framePrefs_t* prefs, uint64_t* frameOffsets,
+                             size_t* failedFrame, void* stream, uint64_t extraFixed, lzgpu_stream_after_fn after, void* afterArg);
+
 /* the thread's error text across calls that may overwrite it: keep is LZK_ERR_BYTES bytes of the caller's */
 static inline void lz_err_save(char* keep) { memcpy(keep, lzk_err(), LZK_ERR_BYTES); }
 static inline void lz_err_restore(const char* keep) { memcpy(lzk_err(), keep, LZK_ERR_BYTES); }

@@ -876,6 +876,17 @@ int   lzk_stream_finish_launch(const LzFramesEntry* d_frames, const LzStreamEntr
     LZ_HIP(hipGetLastError());
     return 0;
 }
+int   lzk_stream_seektable_launch(const LzFramesEntry* d_frames, const LzStreamEntry* d_entries, const LzStreamState* d_state, const uint64_t* d_offsets,
+                                  uint32_t nFrames, uint64_t fixedTotal, uint64_t capacity, hipStream_t stream)
+{
+    if (!d_frames || !d_entries || !d_state || !d_offsets || nFrames == 0) {
+        snprintf(t_err, sizeof t_err, "bad argument (null pointer or no frames)");
+        return -LIZARDGPU_ERR_ARG;
+    }
+    lz_stream_seektable_launch(d_frames, d_entries, d_state, (const u64*)d_offsets, nFrames, fixedTotal, capacity, stream);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
 int   lzk_unframes_walk_launch(const LzUnframesEntry* d_frames, uint32_t nFrames, int fill, uint64_t* d_offs, uint32_t* d_words,
                                struct LzWalkResult* d_res, hipStream_t stream)
 {

@@ -93,6 +93,7 @@ typedef struct LzCtx {
     unsigned long long devPlanesStats[4];          /* LizardGPU_planesStats (lizard_planes_device.c); since process start */
     unsigned long long devBitPlanesStats[4];       /* LizardGPU_bitPlanesStats (lizard_planes_device.c); since process start */
     unsigned long long devPlanesXorStats[4];       /* LizardGPU_planesXorStats (lizard_planes_device.c); since process start */
+    unsigned long long devSeekStats[4];            /* LizardGPU_seekDeviceStats (lizard_seek_device.c); since process start */
     LzStage stage[LZ_STAGES];
     LzCombine comb;
     pthread_mutex_t mu;
@@ -202,6 +203,10 @@ int   lzk_stream_pack_launch(const void* d_base, const uint64_t* d_blkOffsets, c
 int   lzk_stream_finish_launch(const LzFramesEntry* d_frames, const LzStreamEntry* d_entries, const void* d_blob, const LzStreamState* d_state,
                                uint32_t nFrames, uint64_t fixedTotal, uint64_t capacity, LzFramesResult* d_result, uint64_t* d_offsets,
                                hipStream_t stream);
+/* LizardGPU_compressSeekableStream_device (lizard_seek_device.c): behind lzk_stream_finish_launch on the same stream, the seek table
+ * frame of 24 nFrames + 24 bytes at the end of the stream, whose size fixedTotal already counts; nothing after an overflow */
+int   lzk_stream_seektable_launch(const LzFramesEntry* d_frames, const LzStreamEntry* d_entries, const LzStreamState* d_state,
+                                  const uint64_t* d_offsets, uint32_t nFrames, uint64_t fixedTotal, uint64_t capacity, hipStream_t stream);
 /* LizardGPU_decompressFrames_device (lizard_unframes_device.c, unframes_kernels.h): the four launches over a batch of frames in device
  * memory.  walk: one wave per frame whose flags have LZU_WALK (fill = 0: no tables) or LZU_DECODE (fill = 1: frame f's records go to
  * d_offs / d_words + first_f); d_res[f] tells how frame f's walk ended.  decode: record r of frame d_recFrame[r] in place in that

@@ -41,7 +41,9 @@ typedef struct {
     const LizardF_preferences_t* prefsPtr;
     uint64_t* frameOffsets;
     const uint8_t* base;                                      /* the lowest source address among the frames that have blocks */
-    uint64_t fixedTotal;                                      /* every prefix, header, end mark and checksum word of the call */
+    uint64_t fixedTotal;                                      /* every prefix, header, end mark and checksum word of the call, and extraFixed */
+    uint64_t extraFixed;                                      /* bytes the caller of lzgpu_stream_compress writes behind the last frame */
+    lzgpu_stream_after_fn after; void* afterArg;              /* ... from this hook: enqueued on stream B behind the finish kernel */
     int level, hash, launched;
     /* what goes up, in pinned memory (stage 0's h_aux) and in the same layout in device memory (LzCtx::dfTab): the state, the two
      * frame tables, the block tables, the prefix bytes; behind them in dfTab the result record and the frame offsets, which come
@@ -130,7 +132,7 @@ static void s_tables(SJob* j)
             j->h_blkFrames[b] = (uint32_t)i;
         }
     }
-    j->fixedTotal = fixed;
+    j->fixedTotal = fixed + j->extraFixed;
     for (i = F; i-- > 0;) {                                  /* the first frame with blocks at or behind / behind each frame */
         j->h_entries[i].nextAfter = next;
         if (j->h_frames[i].nBlocks) next = (uint32_t)i;
@@ -185,6 +187,8 @@ static int s_enqueue(SJob* j)
     if ((rc = lzk_stream_finish_launch(j->d_frames, j->d_entries, j->d_blob, j->d_state, (uint32_t)j->nFrames, j->fixedTotal, (uint64_t)j->capacity,
                                        j->d_result, j->d_offsets, j->B))) return rc;
     j->launched = 1;
+    if (j->after && (rc = j->after(j->afterArg, j->d_frames, j->d_entries, j->d_state, j->d_offsets, (uint32_t)j->nFrames, j->fixedTotal,
+                                   (uint64_t)j->capacity, j->B))) return rc;
     LZ_HIP(hipMemcpyAsync(j->h_result, j->d_result, j->downBytes, hipMemcpyDeviceToHost, j->B));
     LZ_HIP(hipEventRecord(c->stage[0].meta, j->B));
     return 0;
@@ -202,15 +206,20 @@ size_t LizardGPU_compressStreamBound(size_t nFrames, const size_t* srcSizes, con
     return LizardGPU_frameIsError(sum) ? LZ_FRAME_E(GENERIC) : sum;
 }
 
-size_t LizardGPU_compressStream_device(void* d_dst, size_t dstCapacity, size_t nFrames, const void* const* d_srcs, const size_t* srcSizes,
-                                       const void* const* prefixes, const size_t* prefixSizes, const LizardGPU_framePrefs_t* prefs,
-                                       uint64_t* frameOffsets, size_t* failedFrame, void* stream)
+/* LizardGPU_compressStream_device with room for something behind the last frame: extraFixed bytes join the bytes the host knows
+ * (the returned size, frameOffsets[nFrames] and the one capacity test count them), and `after` (may be NULL) is called once, behind
+ * the launch of lz_stream_finish_kernel, to enqueue on stream B what writes them; it sees the device tables of the call.  With
+ * (0, NULL, NULL) this is the public entry, launch for launch.  lizard_seek_device.c puts the seek table there. */
+size_t lzgpu_stream_compress(void* d_dst, size_t dstCapacity, size_t nFrames, const void* const* d_srcs, const size_t* srcSizes,
+                             const void* const* prefixes, const size_t* prefixSizes, const LizardGPU_framePrefs_t* prefs,
+                             uint64_t* frameOffsets, size_t* failedFrame, void* stream, uint64_t extraFixed, lzgpu_stream_after_fn after,
+                             void* afterArg)
 {
     LizardF_preferences_t plan;
     SJob j;
     LzGuard g;
     size_t i, result = 0;
-    uint64_t fixed = 0;
+    uint64_t fixed = extraFixed;
     int rc;
     lzk_err()[0] = 0;
     if (!nFrames) return 0;
@@ -221,6 +230,7 @@ size_t LizardGPU_compressStream_device(void* d_dst, size_t dstCapacity, size_t n
     memset(&j, 0, sizeof j);
     j.nFrames = nFrames; j.dst = d_dst; j.capacity = dstCapacity; j.srcs = d_srcs; j.sizes = srcSizes; j.prefixes = prefixes; j.prefixSizes = prefixSizes;
     j.prefsPtr = prefs; j.frameOffsets = frameOffsets;
+    j.extraFixed = extraFixed; j.after = after; j.afterArg = afterArg;
     /* the first frame in index order that the single-frame entry would refuse decides, before anything is enqueued */
     for (i = 0; i < nFrames; i++) {
         const size_t pre = prefixSizes ? prefixSizes[i] : 0;
@@ -289,6 +299,14 @@ size_t LizardGPU_compressStream_device(void* d_dst, size_t dstCapacity, size_t n
         lzk_guard_release(&g);
     }
     return rc ? LZ_FRAME_E(GENERIC) : result;
+}
+
+size_t LizardGPU_compressStream_device(void* d_dst, size_t dstCapacity, size_t nFrames, const void* const* d_srcs, const size_t* srcSizes,
+                                       const void* const* prefixes, const size_t* prefixSizes, const LizardGPU_framePrefs_t* prefs,
+                                       uint64_t* frameOffsets, size_t* failedFrame, void* stream)
+{
+    return lzgpu_stream_compress(d_dst, dstCapacity, nFrames, d_srcs, srcSizes, prefixes, prefixSizes, prefs, frameOffsets, failedFrame, stream, 0, NULL,
+                                 NULL);
 }
 
 int LizardGPU_streamCompressDeviceStats(unsigned long long out[4])

@@ -17,10 +17,55 @@
 //                            word at the frame's place, the frame's offset, and (frame 0) the result record.  A frame without blocks
 //                            starts where the next frame that has some starts, or at the stream's end.  After an overflow, or when
 //                            the total passes the capacity, it writes the result record and nothing else.
+//   lz_stream_seektable_kernel  (seekable streams only: LizardGPU_compressSeekableStream_device, lizard_seek_device.c) behind the finish
+//                            kernel, one thread per entry: the seek table frame (include/lizard_amd.h Part 3b) in the last
+//                            tableBytes bytes of the stream, whose size counts them (they are part of fixedTotal).  Entry i is
+//                            { the frame offset the finish kernel wrote, the frame's source size, its prefix bytes, 0 }.  After
+//                            an overflow it writes nothing.  Its body, lz_stream_seektable_item, is written against lz_wave.h's
+//                            types and the tables of lizard_gpu_ctx.h alone, in front of everything that needs hipcc, so the
+//                            CPU SIMT emulator of tests/emul runs it unchanged.
 // The rule of lz_frame_pack.h stays: the scans of successive chunks run in stream order, kernel boundaries (and the host's events)
 // are the only synchronisation, no workgroup waits for another.
 #pragma once
+#include "lz_wave.h"
+#include "lizard_gpu_ctx.h"
+
+// Byte stores: the table starts wherever the last frame ends.
+LZ_DEV void lz_seek_put32(u8* p, u32 v) { p[0] = (u8)v; p[1] = (u8)(v >> 8); p[2] = (u8)(v >> 16); p[3] = (u8)(v >> 24); }
+LZ_DEV void lz_seek_put64(u8* p, u64 v) { lz_seek_put32(p, (u32)v); lz_seek_put32(p + 4, (u32)(v >> 32)); }
+
+// Thread i of nFrames + 1: i < nFrames writes entry i, thread nFrames the frame's 8-byte header and the 16-byte footer.
+// tableBytes = 24 nFrames + 24; total = fixedTotal + carry is the stream's size, the table its last tableBytes bytes.
+LZ_DEV void lz_stream_seektable_item(const LzFramesEntry* frames, const LzStreamEntry* entries, const LzStreamState* state, const u64* offsets,
+                                     u32 nFrames, u64 fixedTotal, u64 capacity, u32 i)
+{
+    const u64 total = fixedTotal + state->carry, tableBytes = 24ull * nFrames + 24ull;
+    if (state->overflow != 0u || total > capacity || i > nFrames) return;      // (below: every byte lies in [total - tableBytes, total))
+    u8* const table = reinterpret_cast<u8*>(frames[0].dst) + (total - tableBytes);
+    if (i < nFrames) {
+        u8* const p = table + 8u + 24ull * i;
+        lz_seek_put64(p, offsets[i]);
+        lz_seek_put64(p + 8, frames[i].srcSize);
+        lz_seek_put32(p + 16, (u32)entries[i].prefixBytes);
+        lz_seek_put32(p + 20, 0u);
+    } else {
+        u8* const foot = table + 8u + 24ull * nFrames;
+        lz_seek_put32(table, 0x184D2A5Eu);                       // LIZARDGPU_SEEK_MAGIC
+        lz_seek_put32(table + 4, (u32)(tableBytes - 8u));
+        lz_seek_put64(foot, (u64)nFrames);
+        lz_seek_put32(foot + 8, 1u);                             // LIZARDGPU_SEEK_VERSION
+        lz_seek_put32(foot + 12, 0x4B535A4Cu);                   // LIZARDGPU_SEEK_TAG "LZSK"
+    }
+}
+
+#ifdef __HIPCC__
 #include "lz_frames_pack.h"
+
+__global__ __launch_bounds__(256) void lz_stream_seektable_kernel(const LzFramesEntry* frames, const LzStreamEntry* entries, const LzStreamState* state,
+                                                                  const u64* offsets, u32 nFrames, u64 fixedTotal, u64 capacity)
+{
+    lz_stream_seektable_item(frames, entries, state, offsets, nFrames, fixedTotal, capacity, blockIdx.x * 256u + threadIdx.x);
+}
 
 // One workgroup of 1024 threads; thread t owns the blocks [lo, hi) of the chunk, block firstBlock + i of the call.
 __global__ __launch_bounds__(1024) void lz_stream_scan_kernel(const u32* sizes, const u32* blkSizes, const u32* blkFrames, u64* offsets,
@@ -106,3 +151,10 @@ static inline void lz_stream_finish_launch(const LzFramesEntry* d_frames, const 
     hipLaunchKernelGGL(lz_stream_finish_kernel, dim3(nFrames), dim3(64), 0, stream, d_frames, d_entries, d_blob, d_state, nFrames, fixedTotal, capacity,
                        d_result, d_offsets);
 }
+static inline void lz_stream_seektable_launch(const LzFramesEntry* d_frames, const LzStreamEntry* d_entries, const LzStreamState* d_state,
+                                              const u64* d_offsets, u32 nFrames, u64 fixedTotal, u64 capacity, hipStream_t stream)
+{
+    hipLaunchKernelGGL(lz_stream_seektable_kernel, dim3(nFrames / 256u + 1u), dim3(256), 0, stream, d_frames, d_entries, d_state, d_offsets, nFrames,
+                       fixedTotal, capacity);
+}
+#endif  // __HIPCC__
