@@ -22,6 +22,8 @@
  *            either of them after an XOR with an earlier version of the buffer, opt-in and per buffer
  *            (LizardGPU_splitPlanesXor_device, LizardGPU_joinPlanesXor_device), and the tensor header, a skippable frame
  *            (LizardGPU_tensorHeaderWrite / Read, with a filter: Write2 / Read2, with a base: Write3 / Read3)
+ *   Part 3d  a row range of a tensor decoded from the blocks that cover it (LizardGPU_planesRangeBytes,
+ *            LizardGPU_decompressFrameRanges_device, LizardGPU_joinPlanesRange_device)
  *
  * Plain C, plain pointers and sizes; no HIP or torch types in any signature (a HIP stream is passed
  * as an opaque void*).
@@ -713,7 +715,8 @@ int LizardGPU_streamDecodeDeviceStats(unsigned long long out[4]);
  * validates): that item's frame does not fill its region, so LizardGPU_decompressSeekableStream_device falls back to the walk and
  * answers for the whole concatenation, and LizardGPU_decompressStreamItems_device refuses that item; the earlier indices name bytes
  * of the FIRST stream there.  Do not read items out of a concatenation; write one table over all items instead.
- * Out of scope: places INSIDE a frame (block-level tables) and element ranges inside a tensor.
+ * Out of scope: places INSIDE a frame (block-level tables).  Element ranges inside a tensor no longer are: Part 3d decodes them from
+ * the blocks that cover them, walking the picked frame's record chain on the device.
  *
  * The host codec (lizard_seek_host.c; no device, no HIP):
  * LizardGPU_seekTableBytes(n): 24 n + 24, the bytes of the table frame for n items, or a code LizardGPU_frameIsError recognises
@@ -956,6 +959,86 @@ typedef struct { uint32_t elemSize; uint32_t ndim; uint64_t nbytes; uint64_t sha
                  uint32_t filter; uint32_t flags; uint64_t baseTag; } LizardGPU_tensorDesc3_t;
 size_t LizardGPU_tensorHeaderWrite3(void* dst, size_t dstCapacity, const LizardGPU_tensorDesc3_t* desc); /* bytes, or 0 */
 int    LizardGPU_tensorHeaderRead3(const void* src, size_t srcSize, LizardGPU_tensorDesc3_t* desc, size_t* headerBytes);
+
+/* ============================================================================================================================
+ * Part 3d — a row range of a tensor, decoded from the blocks that cover it.
+ * ============================================================================================================================
+ * A sharded loader wants rows [start, stop) of every weight.  Every frame this library writes has independent blocks and every
+ * record but the last decodes to exactly the frame's block size B, so byte x of the decoded content lies in record x / B: a reader
+ * decodes the records that cover the bytes it needs and joins that element range only.  Three entries, each usable alone.  Block-level
+ * tables stay out of scope: the record chain of a picked frame is walked on the device, as the batch decoder walks it.
+ *
+ * 1. The arithmetic (lizard_slice_host.c; no device, no HIP).
+ * LizardGPU_planesRangeBytes: the byte ranges [lo, hi) of the SPLIT content that elements [first, last) of a buffer of nElems elements
+ * of elemSize bytes (1, 2, 4 or 8) need, ascending, in PIECE ORDER:
+ *   LIZARDGPU_FILTER_BYTE_PLANES   elemSize ranges, one per plane: [p * nElems + first, p * nElems + last).  An element size of 1 —
+ *                                  also a tensor stored unsplit — is one range.
+ *   LIZARDGPU_FILTER_BIT_PLANES    8 * elemSize + 1 ranges.  With n8 = nElems - nElems % 8 and P = n8 / 8, one per plane:
+ *                                  [k * P + first / 8, k * P + ceil(min(last, n8) / 8)), empty (lo == hi) when first >= min(last, n8);
+ *                                  then one over the raw elements behind n8 * elemSize that belong to the range:
+ *                                  [max(first, n8) * elemSize, last * elemSize) when last > n8, else empty.
+ * Every range holds exactly the bytes in which some element of the range has a bit.  Returns the number of ranges; 0 for a null
+ * `out`, another element size or filter, first > last, last > nElems, or maxOut below that number.
+ * LizardGPU_frameRangesBound: the room the covering blocks of `ranges` take in a frame of block size blockSize: the sum over the
+ * ranges of (ceil(hi / B) - floor(lo / B)) * B, nothing for an empty range.  0 for a null pointer or a block size of 0.
+ *
+ * 2. LizardGPU_decompressFrameRanges_device: of nFrames frames in device memory, decode only the records that cover the byte ranges
+ * ranges[frames[f].firstRange .. + frames[f].nRanges) of frame f's decoded content, into ONE device buffer.  Let full_f be what
+ * LizardGPU_decompressFrame_device decodes for frame f with room enough.  For every frame with results[f] == 0 and every one of its
+ * ranges r = [lo, hi):   d_dst[rangeAt[r] + lo % B + i] == full_f[lo + i] for i < hi - lo,
+ * B being the frame's block size.  The whole covering blocks of range r lie back to back from rangeAt[r], every one in a slot of B
+ * bytes (the last block of a frame fills less of its slot); ranges are placed in index order, rangeAt[nRanges] is the total —
+ * nRanges here being the largest firstRange + nRanges of the call, which `ranges` and `rangeAt` (one entry more) must hold.  An empty
+ * range takes no room and decodes nothing.  A block that two ranges of a frame both touch is decoded once per range: at most one
+ * extra block per range.  Nothing outside d_dst[0 .. dstCapacity) is written, nothing outside a frame's d_src[0 .. srcSize) is read.
+ * In this order: the frames are walked side by side, one wave each (the count pass of LizardGPU_decompressFrames_device); the host
+ * turns the ranges into a list of picked records; the same walk fills the record tables and ONE launch decodes the picks, one wave
+ * each.  The host waits twice per call, whatever the number of frames and ranges.
+ * The total is known after the count pass and is tested against dstCapacity before anything that writes d_dst is launched: a total
+ * above it returns -LIZARDGPU_ERR_ARG with "dstMaxSize_tooSmall" in LizardGPU_lastError and d_dst untouched; a frame refused before
+ * keeps its code, every other answers GENERIC.
+ * The ranges of a frame refused in the count pass take no room.
+ * Per frame, results[f] is 0 or a code LizardGPU_frameIsError recognises; a refused frame does not stop the others and its bytes in
+ * d_dst are unspecified:
+ *   the walk's own code        for a chain it refuses (a cut frame, a bad header ...)
+ *   frameType_unknown          a skippable frame
+ *   frameSize_wrong            a header without content size C on a frame that has records (a frame without records has C = 0); a
+ *                              record count other than ceil(C / B); a range with lo > hi or hi > C
+ *   decompressionFailed        a picked record fails, needs its history (a linked frame), or decodes to anything but B bytes — for the
+ *                              frame's last record, C - (n - 1) * B bytes
+ *   GENERIC                    a null d_src with a non-zero srcSize
+ * A range belongs to at most one frame (else -LIZARDGPU_ERR_ARG); a range of no frame takes no room.
+ * The return value is 0 when the call did its work (LizardGPU_lastError names the first refused frame), -LIZARDGPU_ERR_*
+ * otherwise, and then every results[f] is an error code.
+ * LIMITS, which follow from decoding a part: (1) the content checksum of a frame is NEVER verified here — a slice cannot verify
+ * it; (2) damage in a record that is not picked is not seen; (3) a foreign frame may hold a short record in the middle among the
+ * records that were not picked and still have the right record count — a flushed frame — which cannot be told from a frame of full
+ * blocks without decoding everything: the entry is for frames in which every record but the last fills the block, which is every
+ * frame this library writes.
+ * LizardGPU_sliceDeviceStats: [0] records decoded, [1] frames answered, [2] frames refused, [3] calls; since process start.
+ *
+ * 3. LizardGPU_joinPlanesRange_device: for every item, d_dst[0 .. (last - first) * elemSize) receives
+ * join(the split bytes)[first * elemSize .. last * elemSize) — the join of LizardGPU_joinPlanes_device or
+ * LizardGPU_joinBitPlanes_device, by `filter` — read from PIECES: d_pieces is a HOST array of device addresses, and
+ * d_pieces[firstPiece + q] is the address of the FIRST BYTE of range q of LizardGPU_planesRangeBytes for that item (its `lo`), at any
+ * byte address: a piece starts anywhere inside a decoded block.  An empty range's piece is never read and may be NULL.  With d_base
+ * not NULL the result is XORed with d_base[0 .. (last - first) * elemSize): the caller passes the base already advanced to element
+ * `first`.  ONE launch serves the batch, in the manner of Part 3c: tiles numbered through the batch, a wave per tile, the item found
+ * by bisection.  Nothing outside an item's d_dst bytes is written; nothing is read but the bytes of its ranges and of its base.
+ * Empty items (first == last) are skipped.  -LIZARDGPU_ERR_ARG with nothing launched for a null array, an element size outside
+ * {1, 2, 4, 8}, a filter that is neither, first > last or last > nElems, a null d_dst or a null piece of a non-empty range, or a
+ * batch of 2^32 tiles or more.  `reserved` must be 0.  Column ranges and other strided slices are out of scope. */
+typedef struct { uint64_t lo, hi; } LizardGPU_byteRange_t;
+size_t LizardGPU_planesRangeBytes(uint64_t nElems, uint32_t elemSize, uint32_t filter, uint64_t first, uint64_t last,
+                                  LizardGPU_byteRange_t* out, size_t maxOut);
+size_t LizardGPU_frameRangesBound(const LizardGPU_byteRange_t* ranges, size_t nRanges, size_t blockSize);
+typedef struct { const void* d_src; size_t srcSize; uint32_t firstRange, nRanges; } LizardGPU_sliceFrame_t;
+int LizardGPU_decompressFrameRanges_device(void* d_dst, size_t dstCapacity, size_t nFrames, const LizardGPU_sliceFrame_t* frames,
+                                           const LizardGPU_byteRange_t* ranges, uint64_t* rangeAt /* nRanges + 1, host, out */,
+                                           size_t* results /* nFrames, host: 0 or a frame error code */, void* stream);
+int LizardGPU_sliceDeviceStats(unsigned long long out[4]);
+typedef struct { void* d_dst; const void* d_base; uint64_t nElems, first, last; uint32_t elemSize, filter, firstPiece, reserved; } LizardGPU_planesRange_t;
+int LizardGPU_joinPlanesRange_device(size_t nItems, const LizardGPU_planesRange_t* items, const void* const* d_pieces, void* stream);
 
 #ifdef __cplusplus
 }

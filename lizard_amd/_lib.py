@@ -152,6 +152,13 @@ def lib():
                                                          c.c_uint, c.c_void_p]
     L.LizardGPU_decompressStreamItems_device.restype = c.c_size_t
     L.LizardGPU_seekDeviceStats.argtypes = [c.c_void_p]; L.LizardGPU_seekDeviceStats.restype = c.c_int
+    L.LizardGPU_planesRangeBytes.argtypes = [c.c_uint64, c.c_uint32, c.c_uint32, c.c_uint64, c.c_uint64, c.c_void_p, c.c_size_t]
+    L.LizardGPU_planesRangeBytes.restype = c.c_size_t
+    L.LizardGPU_frameRangesBound.argtypes = [c.c_void_p, c.c_size_t, c.c_size_t]; L.LizardGPU_frameRangesBound.restype = c.c_size_t
+    L.LizardGPU_decompressFrameRanges_device.argtypes = [c.c_void_p, c.c_size_t, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+    L.LizardGPU_decompressFrameRanges_device.restype = c.c_int
+    L.LizardGPU_sliceDeviceStats.argtypes = [c.c_void_p]; L.LizardGPU_sliceDeviceStats.restype = c.c_int
+    L.LizardGPU_joinPlanesRange_device.argtypes = [c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p]; L.LizardGPU_joinPlanesRange_device.restype = c.c_int
     _lib = L
     return L
 

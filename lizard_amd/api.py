@@ -1034,3 +1034,146 @@ def decompress_tensors_device(stream, verify_checksum=True, base=None, base_tag=
     joined = _planes_device(pieces, [int(d.elemSize) for _, _, d in entries], True, [int(d.filter) for _, _, d in entries],
                             [_as_bytes(base[k]) if x else None for k, x in zip(numbers, xored)] if any(xored) else None, xored)
     return [b.view(dt).reshape(tuple(int(s) for s in d.shape[:d.ndim])) for b, dt, (_, _, d) in zip(joined, dtypes, entries)]
+
+
+class _ByteRange(ctypes.Structure):
+    """LizardGPU_byteRange_t."""
+    _fields_ = [("lo", ctypes.c_uint64), ("hi", ctypes.c_uint64)]
+
+
+class _SliceFrame(ctypes.Structure):
+    """LizardGPU_sliceFrame_t."""
+    _fields_ = [("d_src", ctypes.c_void_p), ("srcSize", ctypes.c_size_t), ("firstRange", ctypes.c_uint32), ("nRanges", ctypes.c_uint32)]
+
+
+class _PlanesRange(ctypes.Structure):
+    """LizardGPU_planesRange_t."""
+    _fields_ = [("d_dst", ctypes.c_void_p), ("d_base", ctypes.c_void_p), ("nElems", ctypes.c_uint64), ("first", ctypes.c_uint64),
+                ("last", ctypes.c_uint64), ("elemSize", ctypes.c_uint32), ("filter", ctypes.c_uint32), ("firstPiece", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+def planes_range_bytes(n_elems, elem_size, planes, first, last):
+    """LizardGPU_planesRangeBytes: the byte ranges [(lo, hi)] of the SPLIT content that elements [first, last) of a buffer of n_elems
+    elements of elem_size bytes need, in piece order; planes is "bytes" or "bits".  ValueError for arguments the entry refuses."""
+    L = _lib.lib()
+    out = (_ByteRange * 65)()
+    n = L.LizardGPU_planesRangeBytes(int(n_elems), int(elem_size), _planes_filter(planes, "planes_range_bytes"), int(first), int(last), out, 65)
+    if not n:
+        raise ValueError(f"planes_range_bytes: elements [{first}, {last}) of {n_elems} elements of {elem_size} bytes")
+    return [(int(r.lo), int(r.hi)) for r in out[:n]]
+
+
+def decompress_tensor_slices_device(stream, slices, base=None, base_tag=None):
+    """Rows [start, stop) of some tensors of the SEEKABLE tensor stream in `stream` (a contiguous uint8 CUDA tensor, what
+    compress_tensors_device(..., seekable=True) returns), decoding only the blocks that cover them.  `slices`: a list of
+    (k, start, stop) with k a position in the stream, strictly ascending, and 0 <= start <= stop <= shape[0].  Tensor j of the result
+    equals decompress_tensors_device(stream, select=[k], base=base, base_tag=base_tag)[0][start:stop] — dtype, shape
+    (stop - start, *shape[1:]) and every bit — and the result is a list of views into ONE allocation, each 256-byte aligned.
+    What a tensor-parallel loader does with the whole-tensor entry is decode all of every tensor — the split bytes as a temporary, then
+    the joined tensor — and throw most of it away; here the temporary holds the covering blocks of the range's byte ranges alone (per
+    plane at most two blocks more than the range's share) and the result the range alone.
+    In this order: the seek table; one indexed read of the picked tensor headers; one LizardGPU_framesInfo_device over the picked data
+    frames, for their block sizes; the byte ranges and their bound on the host (LizardGPU_planesRangeBytes, LizardGPU_frameRangesBound);
+    ONE LizardGPU_decompressFrameRanges_device; ONE LizardGPU_joinPlanesRange_device.  No payload byte crosses PCIe.  A stream may mix
+    "LZT1", "LZT2" and "LZT3" tensors, split or not.
+    base: as in decompress_tensors_device — a list indexed by position in the stream, as long as the stream has tensors, of None or the
+    WHOLE base tensor; the slice of the base is taken inside the call.  base_tag as there.
+    ValueError: a 0-dim tensor, start / stop out of order or out of range, positions that do not ascend, a base list of another length.
+    LizardAmdError naming the tensor: a stream without a usable seek table, a frame the slice decoder refuses, a missing or mismatched
+    base, a wrong tag, a header that does not fit its frame — the messages of decompress_tensors_device where the case is the same.
+    LIMITS (include/lizard_amd.h Part 3d): a frame's content checksum is never verified here, because a slice cannot verify it; damage
+    in a block that is not picked is not seen; the frames must have independent blocks that all but the last fill the block size,
+    which is every frame this library writes.  Column ranges and other strided slices are out of scope."""
+    import torch
+    what = "decompress_tensor_slices_device"
+    L = _lib.lib()
+    slices = [(int(k), int(a), int(b)) for k, a, b in slices]
+    for j in range(1, len(slices)):
+        if slices[j][0] <= slices[j - 1][0]:
+            raise ValueError(f"{what}: slices[{j}] names tensor {slices[j][0]}, which does not ascend from slices[{j - 1}]'s {slices[j - 1][0]}")
+    numbers = [k for k, _, _ in slices]
+    entries, count = _tensor_stream_index(stream, what, True, numbers)
+    if base is not None:
+        base = list(base)
+        if len(base) != count:
+            raise ValueError(f"{what}: {len(base)} bases for a stream of {count} tensors")
+    if not entries:
+        return []
+    device = stream.device
+    plans = []                                                  # (dtype, shape, E, filter, n elements, first, last, row bytes, base or None)
+    for (k, start, stop), (h, f, d) in zip(slices, entries):
+        if f["content_size"] != d.nbytes:
+            raise _lib.LizardAmdError(f"{what}: tensor {k}: the header says {d.nbytes} bytes, the frame at offset {f['offset']} decodes to {f['content_size']}")
+        dt = getattr(torch, d.dtype.decode(errors="replace"), None)
+        if not isinstance(dt, torch.dtype):
+            raise _lib.LizardAmdError(f"{what}: tensor {k}: torch knows no dtype {d.dtype.decode(errors='replace')!r}")
+        shape = tuple(int(s) for s in d.shape[:d.ndim])
+        n_items = int(np.prod(shape, dtype=object)) if d.ndim else 1
+        if n_items * torch.empty(0, dtype=dt).element_size() != d.nbytes:
+            raise _lib.LizardAmdError(f"{what}: tensor {k}: shape {shape} of {d.dtype.decode()} is not {d.nbytes} bytes")
+        if not d.ndim:
+            raise ValueError(f"{what}: tensor {k} has no dimension to slice")
+        if not 0 <= start <= stop <= shape[0]:
+            raise ValueError(f"{what}: tensor {k}: rows [{start}, {stop}) of {shape[0]}")
+        E = int(d.elemSize)
+        row = int(d.nbytes) // shape[0] if shape[0] else 0     # (a multiple of E: E divides the dtype's element size)
+        b = None
+        if d.flags & TENSOR_XOR_BASE:
+            b = None if base is None else base[k]
+            if b is None:
+                raise _lib.LizardAmdError(f"{what}: tensor {k}: its header says it was XORed with a base (tag {d.baseTag}), and none was given")
+            if int(b.numel()) * b.element_size() != d.nbytes or b.dtype != dt:
+                raise _lib.LizardAmdError(f"{what}: tensor {k}: its base is {int(b.numel()) * b.element_size()} bytes of {b.dtype}, "
+                                          f"the header says {d.nbytes} bytes of {dt}")
+            if base_tag is not None and int(base_tag) != d.baseTag:
+                raise _lib.LizardAmdError(f"{what}: tensor {k}: the header holds base tag {d.baseTag}, the caller gave {int(base_tag)}")
+            if not (b.is_cuda and b.is_contiguous() and b.device == device):
+                raise _lib.LizardAmdError(f"{what}: tensor {k}: its base is not a contiguous CUDA tensor on {device}")
+        plans.append((dt, shape, E, int(d.filter), int(d.nbytes) // E, start * row // E, stop * row // E, row, b))
+    n = len(plans)
+    L.LizardGPU_setDevice(device.index or 0)
+    hip_stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    # the block size of every picked data frame
+    srcs = (ctypes.c_void_p * n)(*[stream.data_ptr() + f["offset"] for _, f, _ in entries])
+    sizes = (ctypes.c_size_t * n)(*[f["frame_bytes"] for _, f, _ in entries])
+    infos, codes = (_FrameInfo * n)(), (ctypes.c_int * n)()
+    _lib.check(L.LizardGPU_framesInfo_device(n, srcs, sizes, infos, None, None, codes, hip_stream), "LizardGPU_framesInfo_device")
+    for k, rc in zip(numbers, codes):
+        if rc:
+            raise _lib.LizardAmdError(f"{what}: tensor {k}: its data frame is refused: {L.LizardF_getErrorName((1 << 64) + rc).decode()}")
+    # the byte ranges, their frames and the room their covering blocks take
+    ranges, frames, bound = (_ByteRange * (65 * n))(), (_SliceFrame * n)(), 0
+    at = 0
+    for i, (_, _, E, filt, n_elems, first, last, _, _) in enumerate(plans):
+        got = L.LizardGPU_planesRangeBytes(n_elems, E, filt, first, last, ctypes.byref(ranges, at * ctypes.sizeof(_ByteRange)), 65)
+        if not got:
+            raise _lib.LizardAmdError(f"{what}: tensor {numbers[i]}: LizardGPU_planesRangeBytes refused elements [{first}, {last}) of {n_elems}")
+        frames[i].d_src, frames[i].srcSize, frames[i].firstRange, frames[i].nRanges = srcs[i], sizes[i], at, got
+        bound += L.LizardGPU_frameRangesBound(ctypes.byref(ranges, at * ctypes.sizeof(_ByteRange)), got, L.LizardGPU_frameBlockSize(infos[i].blockSizeID))
+        at += got
+    scratch = torch.empty(max(bound, 1), dtype=torch.uint8, device=device)
+    range_at, results = (ctypes.c_uint64 * (at + 1))(), (ctypes.c_size_t * n)()
+    _lib.check(L.LizardGPU_decompressFrameRanges_device(scratch.data_ptr(), bound, n, frames, ranges, range_at, results, hip_stream),
+               "LizardGPU_decompressFrameRanges_device")
+    for k, r in zip(numbers, results):
+        if L.LizardGPU_frameIsError(r):
+            raise _lib.LizardAmdError(f"{what}: tensor {k}: its data frame is refused: {L.LizardF_getErrorName(r).decode()}")
+    # the join of every range out of its pieces, into one result
+    offsets, total = [], 0
+    for _, _, E, _, _, first, last, _, _ in plans:
+        offsets.append(total)
+        total += ((last - first) * E + 255) & ~255
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=device)
+    items, pieces = (_PlanesRange * n)(), (ctypes.c_void_p * at)()
+    for i, ((k, start, _), (_, _, E, filt, n_elems, first, last, row, b)) in enumerate(zip(slices, plans)):
+        B = L.LizardGPU_frameBlockSize(infos[i].blockSizeID)
+        for q in range(frames[i].nRanges):
+            r = frames[i].firstRange + q
+            pieces[r] = scratch.data_ptr() + range_at[r] + ranges[r].lo % B
+        it = items[i]
+        it.d_dst, it.d_base = out.data_ptr() + offsets[i], None if b is None else _as_bytes(b).data_ptr() + start * row
+        it.nElems, it.first, it.last, it.elemSize, it.filter, it.firstPiece = n_elems, first, last, E, filt, frames[i].firstRange
+    _lib.check(L.LizardGPU_joinPlanesRange_device(n, items, pieces, hip_stream), "LizardGPU_joinPlanesRange_device")
+    return [out[o:o + (last - first) * E].view(dt).reshape((stop - start,) + shape[1:])
+            for o, (_, start, stop), (dt, shape, E, _, _, first, last, _, _) in zip(offsets, slices, plans)]

@@ -27,6 +27,8 @@
 #include "unstream_kernels.h"  // the walk across the frames of a stream in device memory (LizardGPU_decompressStream_device)
 #include "planes_kernels.h"    // the bytes of a batch of buffers split into planes and joined again (LizardGPU_splitPlanes_device)
 #include "bitplanes_kernels.h" // ... and their bits (LizardGPU_splitBitPlanes_device)
+#include "unslice_kernels.h"   // the records that cover byte ranges of a batch of frames (LizardGPU_decompressFrameRanges_device)
+#include "planes_range_kernels.h" // an element range joined out of pieces of its planes (LizardGPU_joinPlanesRange_device)
 
 namespace {
 
@@ -602,6 +604,19 @@ int launch_unframes(Ctx& c, const LzUnframesEntry* d_frames, const u64* d_offs, 
     return launch_decode_grid(c, lz_unframes_kernel, a, nRecords, stream);
 }
 
+// The picked records of a batch of frames, each into its slot in ONE destination (unslice_kernels.h).
+int launch_unslice(Ctx& c, const LzUnframesEntry* d_frames, const u64* d_offs, const u32* d_words, const LzSlicePick* d_picks, void* d_dst,
+                   u32* d_out, size_t nPicks, hipStream_t stream)
+{
+    if (!d_frames || !d_offs || !d_words || !d_picks || !d_dst || !d_out || nPicks == 0 || nPicks > 0xFFFFFFFFu) {
+        snprintf(t_err, sizeof t_err, "bad argument (null pointer or no picks)");
+        return -LIZARDGPU_ERR_ARG;
+    }
+    LzUnsliceBatch a;
+    a.frames = d_frames; a.offs = d_offs; a.words = d_words; a.picks = d_picks; a.dst = (u8*)d_dst; a.out = d_out; a.nPicks = (u32)nPicks;
+    return launch_decode_grid(c, lz_unslice_kernel, a, nPicks, stream);
+}
+
 }  // namespace
 
 #include "lizard_shard.h"   // single-process multi-device entry + RCCL size gather (uses Guard / launch above)
@@ -949,6 +964,23 @@ int   lzk_planes_xor_launch(LzCtx* c, const LzPlanesXorEntry* d_tab, uint32_t nE
     void (*const kernel)(const LzPlanesXorEntry*, u32, u32) = bits ? (join ? lz_bitplanes_xor_join_kernel : lz_bitplanes_xor_split_kernel)
                                                                    : (join ? lz_planes_xor_join_kernel : lz_planes_xor_split_kernel);
     hipLaunchKernelGGL(kernel, grid, block, 0, stream, d_tab, nEntries, nTiles);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
+int   lzk_unslice_launch(LzCtx* c, const LzUnframesEntry* d_frames, const uint64_t* d_offs, const uint32_t* d_words, const LzSlicePick* d_picks,
+                         void* d_dst, uint32_t* d_out, size_t nPicks, hipStream_t stream)
+{
+    static_assert(sizeof(LzSlicePick) == 24, "the table the host file fills");
+    return launch_unslice(*c, d_frames, (const u64*)d_offs, d_words, d_picks, d_dst, d_out, nPicks, stream);
+}
+int   lzk_planes_range_launch(LzCtx* c, const LzPlanesRangeEntry* d_tab, uint32_t nEntries, const uint64_t* d_pieces, uint32_t nTiles, hipStream_t stream)
+{
+    static_assert(sizeof(LzPlanesRangeEntry) == 56, "the table the host file fills");
+    if (!d_tab || !d_pieces || nEntries == 0 || nTiles == 0) { snprintf(t_err, sizeof t_err, "bad argument (null pointer or no tiles)"); return -LIZARDGPU_ERR_ARG; }
+    // the grid of lzk_planes_launch
+    const u32 groups = (nTiles + LZP_WAVES - 1u) / LZP_WAVES, cap = (u32)c->cus * 8u;
+    const dim3 grid(groups < cap ? groups : cap), block(64 * LZP_WAVES);
+    hipLaunchKernelGGL(lz_planes_range_kernel, grid, block, 0, stream, d_tab, nEntries, (const u64*)d_pieces, nTiles);
     LZ_HIP(hipGetLastError());
     return 0;
 }

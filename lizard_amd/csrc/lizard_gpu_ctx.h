@@ -94,6 +94,7 @@ typedef struct LzCtx {
     unsigned long long devBitPlanesStats[4];       /* LizardGPU_bitPlanesStats (lizard_planes_device.c); since process start */
     unsigned long long devPlanesXorStats[4];       /* LizardGPU_planesXorStats (lizard_planes_device.c); since process start */
     unsigned long long devSeekStats[4];            /* LizardGPU_seekDeviceStats (lizard_seek_device.c); since process start */
+    unsigned long long devSliceStats[4];           /* LizardGPU_sliceDeviceStats (lizard_slice_device.c); since process start */
     LzStage stage[LZ_STAGES];
     LzCombine comb;
     pthread_mutex_t mu;
@@ -236,6 +237,17 @@ int   lzk_planes_launch(LzCtx* c, const struct LzPlanesEntry* d_tab, uint32_t nE
 /* LizardGPU_splitPlanesXor_device / LizardGPU_joinPlanesXor_device: the same launch over a table of entries with a base each */
 struct LzPlanesXorEntry;
 int   lzk_planes_xor_launch(LzCtx* c, const struct LzPlanesXorEntry* d_tab, uint32_t nEntries, uint32_t nTiles, int join, int bits, hipStream_t stream);
+/* LizardGPU_decompressFrameRanges_device (lizard_slice_device.c, unslice_kernels.h): behind the fill walk of lzk_unframes_walk_launch, pick p
+ * = record d_picks[p].rec of frame d_picks[p].frame decoded to d_dst + d_picks[p].dstOff, a slot of that frame's block size;
+ * d_out[p] = size / 0xFFFFFFFE (needs history) / 0xFFFFFFFF */
+struct LzSlicePick;
+int   lzk_unslice_launch(LzCtx* c, const struct LzUnframesEntry* d_frames, const uint64_t* d_offs, const uint32_t* d_words,
+                         const struct LzSlicePick* d_picks, void* d_dst, uint32_t* d_out, size_t nPicks, hipStream_t stream);
+/* LizardGPU_joinPlanesRange_device (lizard_slice_device.c, planes_range_kernels.h): the one launch over the nTiles tiles of the batch's
+ * nEntries non-empty items, whose table lies at d_tab and whose piece addresses lie at d_pieces */
+struct LzPlanesRangeEntry;
+int   lzk_planes_range_launch(LzCtx* c, const struct LzPlanesRangeEntry* d_tab, uint32_t nEntries, const uint64_t* d_pieces, uint32_t nTiles,
+                              hipStream_t stream);
 /* lizard_pipeline_host.c: its staging helpers, shared with lizard_unframe_host.c */
 int    lzp_ensure_dev(LzCtx* c, void** p, size_t* cap, size_t need);
 int    lzp_ensure_pinned(void** p, size_t* cap, size_t need);
