@@ -58,6 +58,30 @@ static inline void lz_quiesce(LzCtx* c)
     lz_err_restore(keep);
 }
 
+/* nothing of a call that failed on the caller's stream stays in flight there; the error text survives */
+static inline void lz_drain_caller(hipStream_t stream)
+{
+    char keep[LZK_ERR_BYTES];
+    lz_err_save(keep);
+    (void)hipStreamSynchronize(stream);
+    (void)hipGetLastError();
+    lz_err_restore(keep);
+}
+
+/* a table call on the caller's stream: `bytes` of tab go up from pinned memory (stage 0's h_aux) to LzCtx::dfTab, enqueued on stream */
+static inline int lz_table_upload(LzCtx* c, const void* tab, size_t bytes, hipStream_t stream)
+{
+    LzStage* s = c->stage;
+    int rc;
+    if ((rc = lzk_ctx_init(c))) return rc;
+    if ((rc = lzp_ensure_pinned((void**)&s[0].h_aux, &s[0].h_aux_cap, bytes))) return rc;
+    if ((rc = lzp_ensure_dev(c, (void**)&c->dfTab, &c->dfTabCap, bytes))) return rc;
+    memcpy(s[0].h_aux, tab, bytes);
+    c->hostKernelMs = -1.0f;
+    LZ_HIP(hipMemcpyAsync(c->dfTab, s[0].h_aux, bytes, hipMemcpyHostToDevice, stream));
+    return 0;
+}
+
 /* the streams A, B and C of a call start behind what the caller's stream holds */
 static inline int lz_order_after(LzCtx* c, hipStream_t stream, hipStream_t A, hipStream_t B, hipStream_t C)
 {

@@ -941,13 +941,17 @@ int   lzk_unstream_walk_launch(const void* d_src, size_t srcSize, LzStreamCtl* d
     LZ_HIP(hipGetLastError());
     return 0;
 }
+// the grid of the plane kernels: a wave per tile up to eight waves per SIMD, a grid stride over the rest
+static u32 planes_grid(const LzCtx* c, u32 nTiles)
+{
+    const u32 groups = (nTiles + LZP_WAVES - 1u) / LZP_WAVES, cap = (u32)c->cus * 8u;
+    return groups < cap ? groups : cap;
+}
 int   lzk_planes_launch(LzCtx* c, const LzPlanesEntry* d_tab, uint32_t nEntries, uint32_t nTiles, int join, int bits, hipStream_t stream)
 {
     static_assert(sizeof(LzPlanesEntry) == 32, "the table the host file fills");
     if (!d_tab || nEntries == 0 || nTiles == 0) { snprintf(t_err, sizeof t_err, "bad argument (null pointer or no tiles)"); return -LIZARDGPU_ERR_ARG; }
-    // a wave per tile up to eight waves per SIMD, a grid stride over the rest
-    const u32 groups = (nTiles + LZP_WAVES - 1u) / LZP_WAVES, cap = (u32)c->cus * 8u;
-    const dim3 grid(groups < cap ? groups : cap), block(64 * LZP_WAVES);
+    const dim3 grid(planes_grid(c, nTiles)), block(64 * LZP_WAVES);
     void (*const kernel)(const LzPlanesEntry*, u32, u32) = bits ? (join ? lz_bitplanes_join_kernel : lz_bitplanes_split_kernel)
                                                                 : (join ? lz_planes_join_kernel : lz_planes_split_kernel);
     hipLaunchKernelGGL(kernel, grid, block, 0, stream, d_tab, nEntries, nTiles);
@@ -958,9 +962,7 @@ int   lzk_planes_xor_launch(LzCtx* c, const LzPlanesXorEntry* d_tab, uint32_t nE
 {
     static_assert(sizeof(LzPlanesXorEntry) == 40, "the table the host file fills");
     if (!d_tab || nEntries == 0 || nTiles == 0) { snprintf(t_err, sizeof t_err, "bad argument (null pointer or no tiles)"); return -LIZARDGPU_ERR_ARG; }
-    // the grid of lzk_planes_launch
-    const u32 groups = (nTiles + LZP_WAVES - 1u) / LZP_WAVES, cap = (u32)c->cus * 8u;
-    const dim3 grid(groups < cap ? groups : cap), block(64 * LZP_WAVES);
+    const dim3 grid(planes_grid(c, nTiles)), block(64 * LZP_WAVES);
     void (*const kernel)(const LzPlanesXorEntry*, u32, u32) = bits ? (join ? lz_bitplanes_xor_join_kernel : lz_bitplanes_xor_split_kernel)
                                                                    : (join ? lz_planes_xor_join_kernel : lz_planes_xor_split_kernel);
     hipLaunchKernelGGL(kernel, grid, block, 0, stream, d_tab, nEntries, nTiles);
@@ -977,9 +979,7 @@ int   lzk_planes_range_launch(LzCtx* c, const LzPlanesRangeEntry* d_tab, uint32_
 {
     static_assert(sizeof(LzPlanesRangeEntry) == 56, "the table the host file fills");
     if (!d_tab || !d_pieces || nEntries == 0 || nTiles == 0) { snprintf(t_err, sizeof t_err, "bad argument (null pointer or no tiles)"); return -LIZARDGPU_ERR_ARG; }
-    // the grid of lzk_planes_launch
-    const u32 groups = (nTiles + LZP_WAVES - 1u) / LZP_WAVES, cap = (u32)c->cus * 8u;
-    const dim3 grid(groups < cap ? groups : cap), block(64 * LZP_WAVES);
+    const dim3 grid(planes_grid(c, nTiles)), block(64 * LZP_WAVES);
     hipLaunchKernelGGL(lz_planes_range_kernel, grid, block, 0, stream, d_tab, nEntries, (const u64*)d_pieces, nTiles);
     LZ_HIP(hipGetLastError());
     return 0;

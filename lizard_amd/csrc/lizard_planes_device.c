@@ -25,15 +25,8 @@
 /* withBases: the table holds LzPlanesXorEntry (the XOR entries), else LzPlanesEntry. */
 static int planes_locked(LzCtx* c, const void* tab, size_t nEntries, uint32_t nTiles, int join, int bits, int withBases, hipStream_t stream)
 {
-    LzStage* s = c->stage;
-    const size_t bytes = nEntries * (withBases ? sizeof(LzPlanesXorEntry) : sizeof(LzPlanesEntry));
     int rc;
-    if ((rc = lzk_ctx_init(c))) return rc;
-    if ((rc = lzp_ensure_pinned((void**)&s[0].h_aux, &s[0].h_aux_cap, bytes))) return rc;
-    if ((rc = lzp_ensure_dev(c, (void**)&c->dfTab, &c->dfTabCap, bytes))) return rc;
-    memcpy(s[0].h_aux, tab, bytes);
-    c->hostKernelMs = -1.0f;
-    LZ_HIP(hipMemcpyAsync(c->dfTab, s[0].h_aux, bytes, hipMemcpyHostToDevice, stream));
+    if ((rc = lz_table_upload(c, tab, nEntries * (withBases ? sizeof(LzPlanesXorEntry) : sizeof(LzPlanesEntry)), stream))) return rc;
     rc = withBases ? lzk_planes_xor_launch(c, (const LzPlanesXorEntry*)c->dfTab, (uint32_t)nEntries, nTiles, join, bits, stream)
                    : lzk_planes_launch(c, (const LzPlanesEntry*)c->dfTab, (uint32_t)nEntries, nTiles, join, bits, stream);
     if (rc) return rc;
@@ -90,13 +83,8 @@ static int planes(size_t nBuffers, void* const* d_dsts, const void* const* d_src
     lzk_guard_acquire(&g);
     if (g.rc) { free(tab); free(xtab); return g.rc; }
     rc = planes_locked(g.c, withBases ? (const void*)xtab : (const void*)tab, live, (uint32_t)tiles, join, bits, withBases, stream);
-    if (rc) {                                                  /* nothing of this call stays in flight; the error text survives */
-        char keep[LZK_ERR_BYTES];
-        lz_err_save(keep);
-        (void)hipStreamSynchronize(stream);
-        (void)hipGetLastError();
-        lz_err_restore(keep);
-    } else {
+    if (rc) lz_drain_caller(stream);
+    else {
         unsigned long long* const st = withBases ? g.c->devPlanesXorStats : bits ? g.c->devBitPlanesStats : g.c->devPlanesStats;
         st[join ? 1 : 0] += nBuffers;
         st[2] += bytes;

@@ -25,7 +25,7 @@
 #include "../../include/lizard_amd.h"
 #include "lizard_gpu_ctx.h"
 #include "lizard_gpu_shim.h"
-#include "lizard_device_common.h"
+#include "lizard_device_batch.h"
 #include "unslice_kernels.h"
 #include "planes_range_kernels.h"
 
@@ -71,30 +71,6 @@ static int s_buffers(SJob* j, size_t R, size_t K)
     return 0;
 }
 
-/* the stream of the call starts behind what the caller's stream holds; the frame table goes up, every open frame is walked, the walk
- * results come down: the first wait */
-static int s_count_pass(SJob* j, hipStream_t stream)
-{
-    LzStage* s = j->c->stage;
-    size_t i;
-    int rc;
-    for (i = 0; i < j->nFrames; i++) {
-        LzUnframesEntry* e = &j->h_frames[i];
-        memset(e, 0, sizeof *e);
-        if (j->state[i] != S_OPEN) continue;
-        e->src = (uint64_t)(uintptr_t)j->frames[i].d_src; e->srcSize = (uint64_t)j->frames[i].srcSize;
-        e->flags = LZU_WALK;
-    }
-    LZ_HIP(hipEventRecord(s[0].up, stream));
-    LZ_HIP(hipStreamWaitEvent(j->S, s[0].up, 0));
-    LZ_HIP(hipMemcpyAsync(j->d_frames, j->h_frames, j->nFrames * sizeof(LzUnframesEntry), hipMemcpyHostToDevice, j->S));
-    if ((rc = lzk_unframes_walk_launch(j->d_frames, (uint32_t)j->nFrames, 0, NULL, NULL, j->d_walk, j->S))) return rc;
-    LZ_HIP(hipMemcpyAsync(j->h_walk, j->d_walk, j->nFrames * sizeof(LzWalkResult), hipMemcpyDeviceToHost, j->S));
-    LZ_HIP(hipEventRecord(s[0].meta, j->S));
-    LZ_HIP(hipEventSynchronize(s[0].meta));
-    return 0;
-}
-
 /* what the header and the ranges of an open frame say against the rule that byte x lies in record x / B: 0, or the frame's code */
 static size_t s_judge(const SJob* j, size_t f, const LzWalkResult* w)
 {
@@ -110,17 +86,6 @@ static size_t s_judge(const SJob* j, size_t f, const LzWalkResult* w)
     return 0;
 }
 
-static void s_first_refusal(size_t nFrames, const size_t* results)
-{
-    size_t i;
-    for (i = 0; i < nFrames; i++)
-        if (LizardGPU_frameIsError(results[i])) {
-            snprintf(lzk_err(), LZK_ERR_BYTES, "frame %zu refused: %s", i, LizardF_getErrorName(results[i]));
-            return;
-        }
-    lzk_err()[0] = 0;
-}
-
 /* The call under the context guard.  0, or -LIZARDGPU_ERR_*; on 0 every frame is answered. */
 static int s_batch(SJob* j, void* d_dst, size_t dstCapacity, uint64_t* rangeAt, size_t* results, hipStream_t stream)
 {
@@ -131,7 +96,8 @@ static int s_batch(SJob* j, void* d_dst, size_t dstCapacity, uint64_t* rangeAt, 
     if ((rc = lzk_ctx_init(c))) return rc;
     if ((rc = s_buffers(j, 0, 0))) return rc;
     c->hostKernelMs = -1.0f;
-    if ((rc = s_count_pass(j, stream))) return rc;
+    if ((rc = lz_count_pass(c, j->nFrames, j->state, &j->frames[0].d_src, sizeof j->frames[0], &j->frames[0].srcSize, sizeof j->frames[0], j->h_frames,
+                            j->d_frames, j->h_walk, j->d_walk, j->S, stream))) return rc;
     c->devSliceStats[3]++;
     memcpy(j->walk, j->h_walk, j->nFrames * sizeof *j->walk);
     for (i = 0; i < j->nFrames; i++) {
@@ -179,10 +145,7 @@ static int s_batch(SJob* j, void* d_dst, size_t dstCapacity, uint64_t* rangeAt, 
             const uint64_t B = (uint64_t)lzgpu_frame_block_size(w->blockSizeID);
             memset(e, 0, sizeof *e);
             if (j->state[i] != S_OPEN) continue;
-            e->src = (uint64_t)(uintptr_t)x->d_src; e->srcSize = (uint64_t)x->srcSize;
-            e->first = (uint64_t)first; e->nRecords = (uint32_t)w->nRecords;
-            e->contentSize = w->contentSize; e->frameBytes = w->frameBytes; e->maxBlock = (uint32_t)B;
-            e->flags = LZU_DECODE;
+            lz_fill_entry(e, x->d_src, x->srcSize, first, w);
             for (r = 0; r < x->nRanges; r++) {
                 const LizardGPU_byteRange_t* g = &j->ranges[x->firstRange + r];
                 uint64_t b;
@@ -272,7 +235,7 @@ int LizardGPU_decompressFrameRanges_device(void* d_dst, size_t dstCapacity, size
     }
     if (rc) {
         for (i = 0; i < nFrames; i++) if (!LizardGPU_frameIsError(results[i])) results[i] = LZ_FRAME_E(GENERIC);
-    } else s_first_refusal(nFrames, results);
+    } else lz_first_refusal(nFrames, results);
     free(j.state);
     free(j.owner);
     free(j.walk);
@@ -290,15 +253,9 @@ int LizardGPU_sliceDeviceStats(unsigned long long out[4])
 
 static int r_locked(LzCtx* c, const void* tab, size_t nEntries, size_t nPieces, uint32_t nTiles, hipStream_t stream)
 {
-    LzStage* s = c->stage;
-    const size_t oPieces = nEntries * sizeof(LzPlanesRangeEntry), bytes = oPieces + 8 * nPieces;
+    const size_t oPieces = nEntries * sizeof(LzPlanesRangeEntry);
     int rc;
-    if ((rc = lzk_ctx_init(c))) return rc;
-    if ((rc = lzp_ensure_pinned((void**)&s[0].h_aux, &s[0].h_aux_cap, bytes))) return rc;
-    if ((rc = lzp_ensure_dev(c, (void**)&c->dfTab, &c->dfTabCap, bytes))) return rc;
-    memcpy(s[0].h_aux, tab, bytes);
-    c->hostKernelMs = -1.0f;
-    LZ_HIP(hipMemcpyAsync(c->dfTab, s[0].h_aux, bytes, hipMemcpyHostToDevice, stream));
+    if ((rc = lz_table_upload(c, tab, oPieces + 8 * nPieces, stream))) return rc;
     if ((rc = lzk_planes_range_launch(c, (const LzPlanesRangeEntry*)c->dfTab, (uint32_t)nEntries, (const uint64_t*)(c->dfTab + oPieces), nTiles, stream))) return rc;
     LZ_HIP(hipStreamSynchronize(stream));
     return 0;
@@ -354,13 +311,7 @@ int LizardGPU_joinPlanesRange_device(size_t nItems, const LizardGPU_planesRange_
     lzk_guard_acquire(&g);
     if (g.rc) { free(mem); return g.rc; }
     rc = r_locked(g.c, mem, live, nPieces, (uint32_t)tiles, (hipStream_t)stream);
-    if (rc) {                                                  /* nothing of this call stays in flight; the error text survives */
-        char keep[LZK_ERR_BYTES];
-        lz_err_save(keep);
-        (void)hipStreamSynchronize((hipStream_t)stream);
-        (void)hipGetLastError();
-        lz_err_restore(keep);
-    }
+    if (rc) lz_drain_caller((hipStream_t)stream);
     lzk_guard_release(&g);
     free(mem);
     return rc;

@@ -27,84 +27,70 @@
 #include "../../include/lizard_amd.h"
 #include "lizard_gpu_ctx.h"
 #include "lizard_gpu_shim.h"
-#include "lizard_device_common.h"
+#include "lizard_device_batch.h"
 
 #define LZ_STREAM_SLACK 8      /* what every frame gets beyond LizardGPU_compressFrameBound (its known shortfall is 5 bytes) */
 
-/* a stage's device tables (its d_aux): the compressed sizes and the record positions of the chunk it holds */
-static size_t s_aux_bytes(size_t P) { return ((4 * P + 7) & ~(size_t)7) + 8 * P; }
-
 typedef struct {
-    LzCtx* c;
-    size_t nFrames, nBlocks, maxBlock, perChunk, nChunks, prefixTotal, capacity;
+    LzBatch b;                                                /* the blocks of all frames as one list (lizard_device_batch.h) */
+    size_t prefixTotal, capacity;
     void* dst; const void* const* srcs; const size_t* sizes; const void* const* prefixes; const size_t* prefixSizes;
     const LizardF_preferences_t* prefsPtr;
     uint64_t* frameOffsets;
-    const uint8_t* base;                                      /* the lowest source address among the frames that have blocks */
     uint64_t fixedTotal;                                      /* every prefix, header, end mark and checksum word of the call, and extraFixed */
     uint64_t extraFixed;                                      /* bytes the caller of lzgpu_stream_compress writes behind the last frame */
     lzgpu_stream_after_fn after; void* afterArg;              /* ... from this hook: enqueued on stream B behind the finish kernel */
-    int level, hash, launched;
+    int launched;
     /* what goes up, in pinned memory (stage 0's h_aux) and in the same layout in device memory (LzCtx::dfTab): the state, the two
      * frame tables, the block tables, the prefix bytes; behind them in dfTab the result record and the frame offsets, which come
      * down into stage 1's h_aux */
     size_t upBytes, downBytes;
     LzStreamState *h_state, *d_state;
-    LzFramesEntry *h_frames, *d_frames;
     LzStreamEntry *h_entries, *d_entries;
-    uint64_t *h_blkOffsets, *d_blkOffsets;
-    uint32_t *h_blkSizes, *d_blkSizes, *h_blkFrames, *d_blkFrames;
     uint8_t *h_blob, *d_blob;
     LzFramesResult *h_result, *d_result;
     uint64_t *h_offsets, *d_offsets;
-    hipStream_t A, B, C;
 } SJob;
 
 static int s_buffers(SJob* j)
 {
-    LzCtx* c = j->c;
-    const size_t F = j->nFrames, T = j->nBlocks, P = T < j->perChunk ? T : j->perChunk;
+    LzBatch* b = &j->b;
+    LzCtx* c = b->c;
+    const size_t F = b->nFrames;
     const size_t oFrames = sizeof(LzStreamState), oEntries = oFrames + F * sizeof(LzFramesEntry), oOff = oEntries + F * sizeof(LzStreamEntry),
-                 oSizes = oOff + 8 * T, oBlkFrames = oSizes + 4 * T, oBlob = (oBlkFrames + 4 * T + 7) & ~(size_t)7;
-    size_t s;
+                 oBlob = lz_batch_tables_end(b, oOff);
     int rc;
     j->upBytes = (oBlob + j->prefixTotal + 8) & ~(size_t)7;                       /* (never empty behind oBlob: the blob's address is a valid one) */
     j->downBytes = sizeof(LzFramesResult) + (j->frameOffsets ? 8 * (F + 1) : 0);
     if ((rc = lzp_ensure_pinned((void**)&c->stage[0].h_aux, &c->stage[0].h_aux_cap, j->upBytes))) return rc;
     if ((rc = lzp_ensure_pinned((void**)&c->stage[1].h_aux, &c->stage[1].h_aux_cap, sizeof(LzFramesResult) + 8 * (F + 1)))) return rc;
     if ((rc = lzp_ensure_dev(c, (void**)&c->dfTab, &c->dfTabCap, j->upBytes + sizeof(LzFramesResult) + 8 * (F + 1)))) return rc;
-    for (s = 0; s < LZ_STAGES && s < j->nChunks; s++) {
-        if ((rc = lzp_ensure_dev(c, (void**)&c->stage[s].d_slots, &c->stage[s].d_slots_cap, P * lz_bound_slot(j->maxBlock)))) return rc;
-        if ((rc = lzp_ensure_dev(c, (void**)&c->stage[s].d_aux, &c->stage[s].d_aux_cap, s_aux_bytes(P)))) return rc;
-    }
+    if ((rc = lz_batch_stages(b))) return rc;
     j->h_state = (LzStreamState*)c->stage[0].h_aux;                  j->d_state = (LzStreamState*)c->dfTab;
-    j->h_frames = (LzFramesEntry*)(c->stage[0].h_aux + oFrames);     j->d_frames = (LzFramesEntry*)(c->dfTab + oFrames);
+    b->h_frames = (LzFramesEntry*)(c->stage[0].h_aux + oFrames);     b->d_frames = (LzFramesEntry*)(c->dfTab + oFrames);
     j->h_entries = (LzStreamEntry*)(c->stage[0].h_aux + oEntries);   j->d_entries = (LzStreamEntry*)(c->dfTab + oEntries);
-    j->h_blkOffsets = (uint64_t*)(c->stage[0].h_aux + oOff);         j->d_blkOffsets = (uint64_t*)(c->dfTab + oOff);
-    j->h_blkSizes = (uint32_t*)(c->stage[0].h_aux + oSizes);         j->d_blkSizes = (uint32_t*)(c->dfTab + oSizes);
-    j->h_blkFrames = (uint32_t*)(c->stage[0].h_aux + oBlkFrames);    j->d_blkFrames = (uint32_t*)(c->dfTab + oBlkFrames);
+    lz_batch_block_tables(b, c->stage[0].h_aux, c->dfTab, oOff);
     j->h_blob = c->stage[0].h_aux + oBlob;                           j->d_blob = c->dfTab + oBlob;
     j->h_result = (LzFramesResult*)c->stage[1].h_aux;                j->d_result = (LzFramesResult*)(c->dfTab + j->upBytes);
     j->h_offsets = (uint64_t*)(c->stage[1].h_aux + sizeof(LzFramesResult));
     j->d_offsets = (uint64_t*)(c->dfTab + j->upBytes + sizeof(LzFramesResult));
-    j->A = c->stage[0].stream; j->B = c->stage[1].stream; j->C = c->stage[2].stream;
     return 0;
 }
 
 /* the state, the per-frame and the per-block tables and the prefix bytes, in pinned memory */
 static void s_tables(SJob* j)
 {
-    const size_t F = j->nFrames;
+    const size_t F = j->b.nFrames;
     size_t i, b = 0, blob = 0;
     uint64_t fixed = 0;
     uint32_t next = (uint32_t)F;
     memset(j->h_state, 0, sizeof *j->h_state);
     for (i = 0; i < F; i++) {
-        LzFramesEntry* e = &j->h_frames[i];
+        LzFramesEntry* e = &j->b.h_frames[i];
         LzStreamEntry* s = &j->h_entries[i];
         LizardF_preferences_t prefs;
         const size_t pre = j->prefixSizes ? j->prefixSizes[i] : 0;
-        size_t bs, nb, k;
+        size_t bs, nb;
         memset(e, 0, sizeof *e);
         memset(s, 0, sizeof *s);
         (void)lzgpu_frame_device_plan(&prefs, j->prefsPtr, j->dst, LizardGPU_compressFrameBound(j->sizes[i], j->prefsPtr) + LZ_STREAM_SLACK, j->srcs[i],
@@ -126,71 +112,38 @@ static void s_tables(SJob* j)
         fixed += s->tailBytes;
         s->firstBlock = nb ? (uint32_t)b : 0xFFFFFFFFu;
         s->lastBlock = nb ? (uint32_t)(b + nb - 1) : 0xFFFFFFFFu;
-        for (k = 0; k < nb; k++, b++) {
-            j->h_blkOffsets[b] = (uint64_t)((const uint8_t*)j->srcs[i] + k * bs - j->base);
-            j->h_blkSizes[b] = (uint32_t)(k + 1 == nb ? j->sizes[i] - k * bs : bs);
-            j->h_blkFrames[b] = (uint32_t)i;
-        }
+        lz_batch_blocks(&j->b, &b, i, j->srcs[i], j->sizes[i], bs, nb);
     }
     j->fixedTotal = fixed + j->extraFixed;
     for (i = F; i-- > 0;) {                                  /* the first frame with blocks at or behind / behind each frame */
         j->h_entries[i].nextAfter = next;
-        if (j->h_frames[i].nBlocks) next = (uint32_t)i;
+        if (j->b.h_frames[i].nBlocks) next = (uint32_t)i;
         j->h_entries[i].nextSelf = next;
     }
 }
 
-/* stream B starts behind what the caller's stream holds and uploads the tables; A and C start behind the upload */
-static int s_upload(SJob* j, hipStream_t stream)
+/* a chunk's records get their places behind the carry and move there (lz_batch_rotate's pack) */
+static int s_pack(void* arg, const LzBatch* b, const LzStage* s, size_t first, size_t q, size_t bs, uint32_t* d_sizes, uint64_t* d_offsets)
 {
-    LzStage* s = j->c->stage;
-    LZ_HIP(hipEventRecord(s[0].up, stream));
-    LZ_HIP(hipStreamWaitEvent(j->B, s[0].up, 0));
-    LZ_HIP(hipMemcpyAsync(j->d_state, j->h_state, j->upBytes, hipMemcpyHostToDevice, j->B));
-    LZ_HIP(hipEventRecord(s[1].up, j->B));
-    LZ_HIP(hipStreamWaitEvent(j->A, s[1].up, 0));
-    LZ_HIP(hipStreamWaitEvent(j->C, s[1].up, 0));
-    return 0;
+    const SJob* j = (const SJob*)arg;
+    return lzk_stream_pack_launch(b->base, b->d_blkOffsets + first, b->d_blkSizes + first, b->d_blkFrames + first, s->d_slots, lz_bound_slot(bs), d_sizes,
+                                  d_offsets, (uint32_t)q, (uint32_t)first, b->d_frames, j->d_entries, j->d_state, (uint64_t)j->capacity, b->B);
 }
 
 /* every chunk, the hash, the finish and the copy of the result record and the offsets: enqueued, nothing waited for */
 static int s_enqueue(SJob* j)
 {
-    LzCtx* c = j->c;
-    const size_t P = j->nBlocks < j->perChunk ? j->nBlocks : j->perChunk;
-    size_t k;
+    LzBatch* b = &j->b;
+    LzCtx* c = b->c;
     int rc;
-    if (j->hash) {
-        if ((rc = lzk_frames_hash_launch(j->d_frames, (uint32_t)j->nFrames, j->C))) return rc;
-        j->launched = 1;
-        LZ_HIP(hipEventRecord(c->stage[2].up, j->C));
-    }
-    for (k = 0; k < j->nChunks; k++) {
-        LzStage* s = &c->stage[k % LZ_STAGES];
-        const size_t first = k * j->perChunk, q = j->nBlocks - first < j->perChunk ? j->nBlocks - first : j->perChunk;
-        uint32_t* const d_sizes = (uint32_t*)s->d_aux;
-        uint64_t* const d_offsets = (uint64_t*)(s->d_aux + ((4 * P + 7) & ~(size_t)7));
-        size_t bs = 0, b;
-        for (b = first; b < first + q; b++) if (j->h_frames[j->h_blkFrames[b]].blockSize > bs) bs = j->h_frames[j->h_blkFrames[b]].blockSize;
-        if (k >= LZ_STAGES) LZ_HIP(hipStreamWaitEvent(j->A, s->done, 0));      /* the slots and tables are free once chunk k - 3 is gathered */
-        if ((rc = lzk_launch(c, j->base, q, bs, bs, s->d_slots, lz_bound_slot(bs), d_sizes, j->level, j->A, s->k0, s->k1, j->d_blkSizes + first,
-                             j->d_blkOffsets + first))) return rc;
-        j->launched = 1;
-        LZ_HIP(hipStreamWaitEvent(j->B, s->k1, 0));
-        if ((rc = lzk_stream_pack_launch(j->base, j->d_blkOffsets + first, j->d_blkSizes + first, j->d_blkFrames + first, s->d_slots, lz_bound_slot(bs),
-                                         d_sizes, d_offsets, (uint32_t)q, (uint32_t)first, j->d_frames, j->d_entries, j->d_state,
-                                         (uint64_t)j->capacity, j->B))) return rc;
-        LZ_HIP(hipEventRecord(s->done, j->B));
-        c->devStreamCompressStats[2]++;
-    }
-    if (j->hash) LZ_HIP(hipStreamWaitEvent(j->B, c->stage[2].up, 0));
-    if ((rc = lzk_stream_finish_launch(j->d_frames, j->d_entries, j->d_blob, j->d_state, (uint32_t)j->nFrames, j->fixedTotal, (uint64_t)j->capacity,
-                                       j->d_result, j->d_offsets, j->B))) return rc;
+    if ((rc = lz_batch_rotate(b, s_pack, j, &c->devStreamCompressStats[2], &j->launched))) return rc;
+    if ((rc = lzk_stream_finish_launch(b->d_frames, j->d_entries, j->d_blob, j->d_state, (uint32_t)b->nFrames, j->fixedTotal, (uint64_t)j->capacity,
+                                       j->d_result, j->d_offsets, b->B))) return rc;
     j->launched = 1;
-    if (j->after && (rc = j->after(j->afterArg, j->d_frames, j->d_entries, j->d_state, j->d_offsets, (uint32_t)j->nFrames, j->fixedTotal,
-                                   (uint64_t)j->capacity, j->B))) return rc;
-    LZ_HIP(hipMemcpyAsync(j->h_result, j->d_result, j->downBytes, hipMemcpyDeviceToHost, j->B));
-    LZ_HIP(hipEventRecord(c->stage[0].meta, j->B));
+    if (j->after && (rc = j->after(j->afterArg, b->d_frames, j->d_entries, j->d_state, j->d_offsets, (uint32_t)b->nFrames, j->fixedTotal,
+                                   (uint64_t)j->capacity, b->B))) return rc;
+    LZ_HIP(hipMemcpyAsync(j->h_result, j->d_result, j->downBytes, hipMemcpyDeviceToHost, b->B));
+    LZ_HIP(hipEventRecord(c->stage[0].meta, b->B));
     return 0;
 }
 
@@ -228,7 +181,7 @@ size_t lzgpu_stream_compress(void* d_dst, size_t dstCapacity, size_t nFrames, co
         return LZ_FRAME_E(GENERIC);
     }
     memset(&j, 0, sizeof j);
-    j.nFrames = nFrames; j.dst = d_dst; j.capacity = dstCapacity; j.srcs = d_srcs; j.sizes = srcSizes; j.prefixes = prefixes; j.prefixSizes = prefixSizes;
+    j.b.nFrames = nFrames; j.dst = d_dst; j.capacity = dstCapacity; j.srcs = d_srcs; j.sizes = srcSizes; j.prefixes = prefixes; j.prefixSizes = prefixSizes;
     j.prefsPtr = prefs; j.frameOffsets = frameOffsets;
     j.extraFixed = extraFixed; j.after = after; j.afterArg = afterArg;
     /* the first frame in index order that the single-frame entry would refuse decides, before anything is enqueued */
@@ -244,17 +197,17 @@ size_t lzgpu_stream_compress(void* d_dst, size_t dstCapacity, size_t nFrames, co
         {
             const size_t bs = lzgpu_frame_block_size((unsigned)plan.frameInfo.blockSizeID), nb = (srcSizes[i] + bs - 1) / bs;
             uint8_t header[20];
-            j.hash = plan.frameInfo.contentChecksumFlag == 1;
-            j.level = lzk_clamp_level(plan.compressionLevel);
+            j.b.hash = plan.frameInfo.contentChecksumFlag == 1;
+            j.b.level = lzk_clamp_level(plan.compressionLevel);
             j.prefixTotal += pre;
-            fixed += pre + lzgpu_frame_write_header(header, &plan.frameInfo) + 4u + (j.hash ? 4u : 0u);
+            fixed += pre + lzgpu_frame_write_header(header, &plan.frameInfo) + 4u + (j.b.hash ? 4u : 0u);
             if (!nb) continue;
-            j.nBlocks += nb;
-            if (bs > j.maxBlock) j.maxBlock = bs;
-            if (!j.base || (const uint8_t*)d_srcs[i] < j.base) j.base = (const uint8_t*)d_srcs[i];
+            j.b.nBlocks += nb;
+            if (bs > j.b.maxBlock) j.b.maxBlock = bs;
+            if (!j.b.base || (const uint8_t*)d_srcs[i] < j.b.base) j.b.base = (const uint8_t*)d_srcs[i];
         }
     }
-    if (j.nBlocks > 0xFFFFFFFFu) {
+    if (j.b.nBlocks > 0xFFFFFFFFu) {
         snprintf(lzk_err(), LZK_ERR_BYTES, "bad argument (more than 2^32 - 1 blocks in one stream)");
         return LZ_FRAME_E(GENERIC);
     }
@@ -262,21 +215,21 @@ size_t lzgpu_stream_compress(void* d_dst, size_t dstCapacity, size_t nFrames, co
         snprintf(lzk_err(), LZK_ERR_BYTES, "the stream needs more than dstCapacity = %zu bytes", dstCapacity);
         return LZ_FRAME_E(dstMaxSize_tooSmall);
     }
-    if (!j.base) j.base = (const uint8_t*)d_dst;             /* (no frame has a block: no launch reads through it) */
+    if (!j.b.base) j.b.base = (const uint8_t*)d_dst;             /* (no frame has a block: no launch reads through it) */
     lzk_guard_acquire(&g);
     rc = g.rc;
     if (!rc) {
-        j.c = g.c;
+        j.b.c = g.c;
         rc = lzk_ctx_init(g.c);
         if (!rc) {
-            j.perChunk = lz_frame_chunk_blocks(g.c, j.maxBlock ? j.maxBlock : lzgpu_frame_block_size(1));
-            j.nChunks = (j.nBlocks + j.perChunk - 1) / j.perChunk;
+            j.b.perChunk = lz_frame_chunk_blocks(g.c, j.b.maxBlock ? j.b.maxBlock : lzgpu_frame_block_size(1));
+            j.b.nChunks = (j.b.nBlocks + j.b.perChunk - 1) / j.b.perChunk;
             rc = s_buffers(&j);
         }
         if (!rc) {
             s_tables(&j);
             g.c->hostKernelMs = -1.0f;
-            rc = s_upload(&j, (hipStream_t)stream);
+            rc = lz_batch_upload(&j.b, j.d_state, j.h_state, j.upBytes, (hipStream_t)stream);
         }
         if (!rc) rc = s_enqueue(&j);
         if (!rc) {                                           /* the only wait of the call */

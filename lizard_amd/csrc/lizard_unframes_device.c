@@ -31,8 +31,7 @@
 #include "../../include/lizard_amd.h"
 #include "lizard_gpu_ctx.h"
 #include "lizard_gpu_shim.h"
-#include "lizard_device_common.h"
-#include "unframes_kernels.h"
+#include "lizard_device_batch.h"
 
 enum { U_OPEN = 0, U_DECIDED = 1, U_DELEGATE = 2 };           /* a frame's state on the host */
 
@@ -78,33 +77,11 @@ static int u_buffers(UJob* j, size_t R)
     return 0;
 }
 
-/* the frame table of the count pass: every frame the host has not answered is walked */
-static void u_count_table(UJob* j)
-{
-    size_t i;
-    for (i = 0; i < j->nFrames; i++) {
-        LzUnframesEntry* e = &j->h_frames[i];
-        memset(e, 0, sizeof *e);
-        if (j->state[i] != U_OPEN) continue;
-        e->src = (uint64_t)(uintptr_t)j->srcs[i]; e->srcSize = (uint64_t)j->sizes[i];
-        e->flags = LZU_WALK;
-    }
-}
-
-/* the stream of the call starts behind what the caller's stream holds; the frame table goes up, every frame is walked, the walk
- * results come down: the first wait */
+/* the count pass over every frame the host has not answered: the first wait */
 static int u_count_pass(UJob* j, hipStream_t stream)
 {
-    LzStage* s = j->c->stage;
-    int rc;
-    LZ_HIP(hipEventRecord(s[0].up, stream));
-    LZ_HIP(hipStreamWaitEvent(j->S, s[0].up, 0));
-    LZ_HIP(hipMemcpyAsync(j->d_frames, j->h_frames, j->nFrames * sizeof(LzUnframesEntry), hipMemcpyHostToDevice, j->S));
-    if ((rc = lzk_unframes_walk_launch(j->d_frames, (uint32_t)j->nFrames, 0, NULL, NULL, j->d_walk, j->S))) return rc;
-    LZ_HIP(hipMemcpyAsync(j->h_walk, j->d_walk, j->nFrames * sizeof(LzWalkResult), hipMemcpyDeviceToHost, j->S));
-    LZ_HIP(hipEventRecord(s[0].meta, j->S));
-    LZ_HIP(hipEventSynchronize(s[0].meta));
-    return 0;
+    return lz_count_pass(j->c, j->nFrames, j->state, j->srcs, sizeof j->srcs[0], j->sizes, sizeof j->sizes[0], j->h_frames, j->d_frames, j->h_walk,
+                         j->d_walk, j->S, stream);
 }
 
 /* the tables of the fill pass, from the caller's arrays and the walk results (the pinned table may have moved since the count pass) */
@@ -118,12 +95,9 @@ static void u_fill_tables(UJob* j)
         memset(e, 0, sizeof *e);
         memset(h, 0, sizeof *h);
         if (j->state[i] != U_OPEN) continue;
-        e->src = (uint64_t)(uintptr_t)j->srcs[i]; e->srcSize = (uint64_t)j->sizes[i];
+        lz_fill_entry(e, j->srcs[i], j->sizes[i], first, w);
         e->dst = (uint64_t)(uintptr_t)j->dsts[i]; e->cap = (uint64_t)j->caps[i];
-        e->first = (uint64_t)first; e->nRecords = (uint32_t)w->nRecords;
-        e->contentSize = w->contentSize; e->frameBytes = w->frameBytes;
-        e->maxBlock = (uint32_t)lzgpu_frame_block_size(w->blockSizeID);
-        e->flags = LZU_DECODE | (w->checksumFlag && !(j->flags & LIZARDGPU_FRAME_SKIP_CHECKSUM) ? LZU_VERIFY : 0u);
+        if (w->checksumFlag && !(j->flags & LIZARDGPU_FRAME_SKIP_CHECKSUM)) e->flags |= LZU_VERIFY;
         h->src = e->dst;                                        /* srcSize: the settle kernel's to write */
         if (e->flags & LZU_VERIFY) h->flags = LZK_FRAMES_LIVE | LZK_FRAMES_CHECKSUM;
         for (k = 0; k < (size_t)w->nRecords; k++) j->h_recFrame[first + k] = (uint32_t)i;
@@ -151,17 +125,6 @@ static int u_fill_pass(UJob* j, int anyHash)
     return 0;
 }
 
-static void u_first_refusal(size_t nFrames, const size_t* results)      /* the error text of a call that did its work: the first frame that was refused */
-{
-    size_t i;
-    for (i = 0; i < nFrames; i++)
-        if (LizardGPU_frameIsError(results[i])) {
-            snprintf(lzk_err(), LZK_ERR_BYTES, "frame %zu refused: %s", i, LizardF_getErrorName(results[i]));
-            return;
-        }
-    lzk_err()[0] = 0;
-}
-
 /* The batch part under the context guard.  0, or -LIZARDGPU_ERR_*; on 0 every frame is U_DECIDED (answered) or U_DELEGATE. */
 static int u_batch(UJob* j, size_t* results, size_t* consumed, hipStream_t stream)
 {
@@ -170,7 +133,6 @@ static int u_batch(UJob* j, size_t* results, size_t* consumed, hipStream_t strea
     int rc, anyHash = 0;
     if ((rc = lzk_ctx_init(c))) return rc;
     if ((rc = u_buffers(j, 0))) return rc;
-    u_count_table(j);
     c->hostKernelMs = -1.0f;
     if ((rc = u_count_pass(j, stream))) return rc;
     c->devFramesDecodeStats[3]++;
@@ -261,7 +223,7 @@ int LizardGPU_decompressFrames_device(size_t nFrames, void* const* d_dsts, const
         if (srcConsumed) srcConsumed[i] = used;
     }
     free(j.state);
-    u_first_refusal(nFrames, results);
+    lz_first_refusal(nFrames, results);
     return 0;
 }
 
@@ -295,7 +257,7 @@ int LizardGPU_framesInfo_device(size_t nFrames, const void* const* d_srcs, const
             j.c = g.c;
             rc = lzk_ctx_init(g.c);
             if (!rc) rc = u_buffers(&j, 0);
-            if (!rc) { u_count_table(&j); rc = u_count_pass(&j, (hipStream_t)stream); }
+            if (!rc) rc = u_count_pass(&j, (hipStream_t)stream);
             for (i = 0; i < nFrames && !rc; i++) {
                 const LzWalkResult* w = &j.h_walk[i];
                 if (j.state[i] != U_OPEN) continue;

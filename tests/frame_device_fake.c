@@ -15,10 +15,9 @@
 #include <string.h>
 
 #include "../lizard_amd/csrc/lizard_frame_device.c"        /* unit under test, compiled into this harness */
-#include "fake_hip.h"
+#include "device_fake_common.h"
 
-static int g_refusePack;
-void pf_refuse_frame_pack(int nth) { LzGuard g; lzk_guard_acquire(&g); g_refusePack = nth; lzk_guard_release(&g); }
+void pf_refuse_frame_pack(int nth) { dfc_refuse_set(0, nth); }
 
 typedef struct { const uint8_t *in, *slots; size_t slot; const uint32_t* sizes; uint64_t* offsets; uint8_t* dst; uint32_t nb, blockSize, last; uint64_t* state; uint64_t limit; } FramePackK;
 static void frame_pack_kernel(void* a)
@@ -55,7 +54,7 @@ int lzk_frame_pack_launch(const void* d_in, const void* d_slots, size_t slot, co
     if (!d_in || !d_slots || !d_sizes || !d_offsets || !d_dst || !d_state || nb == 0 || blockSize == 0 || lastBlockSize == 0 || lastBlockSize > blockSize) {
         snprintf(lzk_err(), LZK_ERR_BYTES, "lzk_frame_pack_launch: bad argument"); return -LIZARDGPU_ERR_ARG;
     }
-    if (g_refusePack && !--g_refusePack) { snprintf(lzk_err(), LZK_ERR_BYTES, "lzk_frame_pack_launch: refused by the test"); return -LIZARDGPU_ERR_HIP; }
+    if (dfc_refused(0, "lzk_frame_pack_launch")) return -LIZARDGPU_ERR_HIP;
     k.in = (const uint8_t*)d_in; k.slots = (const uint8_t*)d_slots; k.slot = slot; k.sizes = d_sizes; k.offsets = d_offsets; k.dst = (uint8_t*)d_dst;
     k.nb = nb; k.blockSize = blockSize; k.last = lastBlockSize; k.state = d_state; k.limit = limit;
     return fh_enqueue_kernel(stream, frame_pack_kernel, &k, sizeof k) == hipSuccess ? 0 : -LIZARDGPU_ERR_HIP;
@@ -66,10 +65,7 @@ int lzk_frame_pack_launch(const void* d_in, const void* d_slots, size_t slot, co
 #include "lizard_oracle.h"
 void pf_set_chunk_bytes(size_t n);
 void pf_shutdown(void);
-#define CHECK(cond, ...) do { if (!(cond)) { fprintf(stderr, "frame_device_fake: line %d: ", __LINE__); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); return 1; } } while (0)
-#define FERR(code) ((size_t)-(long)(LIZARDGPU_FRAME_ERR_##code))
-#define DV_G 4096
-static hipStream_t g_user;
+#define CHECK(cond, ...) DFC_CHECK("frame_device_fake", cond, __VA_ARGS__)
 static int g_failMalloc;          /* the n-th hipMalloc inside the next device call fails */
 
 /* both entries on the same bytes: the same answer, the same frame, the margins of d_dst and d_src untouched.  capDelta: capacity
@@ -78,35 +74,29 @@ static int g_failMalloc;          /* the n-th hipMalloc inside the next device c
 static int both(const uint8_t* data, size_t n, int level, int bsid, int checksum, int csize, long capDelta, size_t want)
 {
     LizardF_preferences_t p;
-    uint8_t *dsrc = NULL, *ddst = NULL, *hsrc = NULL, *hdst = NULL, *twin;
-    size_t bound, cap, sn = n + 2 * DV_G, dn, r, t, i;
+    const hipStream_t user = dfc_user();
+    Region src, dst;
+    uint8_t* twin;
+    size_t bound, cap, r, t;
     int bad = 0;
     memset(&p, 0, sizeof p);
     p.frameInfo.blockSizeID = (LizardF_blockSizeID_t)bsid; p.frameInfo.blockMode = (LizardF_blockMode_t)1;
     p.frameInfo.contentChecksumFlag = (LizardF_contentChecksum_t)checksum; p.frameInfo.contentSize = csize ? n : 0; p.compressionLevel = level;
     bound = LizardGPU_compressFrameBound(n, &p);
-    cap = (size_t)((long)bound + capDelta); dn = cap + 2 * DV_G;
+    cap = (size_t)((long)bound + capDelta);
     twin = (uint8_t*)malloc(cap + 1);
-    CHECK(hipMalloc((void**)&dsrc, sn) == hipSuccess && hipMalloc((void**)&ddst, dn) == hipSuccess
-          && hipHostMalloc((void**)&hsrc, sn, 0) == hipSuccess && hipHostMalloc((void**)&hdst, dn, 0) == hipSuccess, "allocation");
-    memset(hsrc, 0x5A, sn); if (n) memcpy(hsrc + DV_G, data, n);
-    memset(hdst, 0xC3, dn);
-    if (!g_user) hipStreamCreateWithFlags(&g_user, hipStreamNonBlocking);
-    hipMemcpyAsync(dsrc, hsrc, sn, hipMemcpyHostToDevice, g_user); hipMemcpyAsync(ddst, hdst, dn, hipMemcpyHostToDevice, g_user);
-    if (g_failMalloc) hipStreamSynchronize(g_user);        /* (a call that fails before it orders itself behind the caller's stream leaves that stream's work queued, as it may) */
+    CHECK(!region_make(&src, data, n, 0, 0x5A) && !region_make(&dst, NULL, cap, 0, 0xC3), "allocation");
+    if (g_failMalloc) hipStreamSynchronize(user);        /* (a call that fails before it orders itself behind the caller's stream leaves that stream's work queued, as it may) */
     fh_fail_malloc(g_failMalloc);
-    r = LizardGPU_compressFrame_device(ddst + DV_G, cap, dsrc + DV_G, n, &p, g_user);
+    r = LizardGPU_compressFrame_device(region_at(&dst), cap, region_at(&src), n, &p, user);
     fh_fail_malloc(0); g_failMalloc = 0;
     t = LizardGPU_compressFrame(twin, cap, data, n, &p);
-    hipStreamSynchronize(g_user);                          /* (a call refused up front never touched the caller's stream: the uploads may still be queued) */
-    memset(hdst, 0, dn); memset(hsrc, 0, sn);
-    hipMemcpy(hdst, ddst, dn, hipMemcpyDeviceToHost); hipMemcpy(hsrc, dsrc, sn, hipMemcpyDeviceToHost);
-    for (i = 0; i < DV_G; i++) bad |= hdst[i] != 0xC3 || hdst[DV_G + cap + i] != 0xC3 || hsrc[i] != 0x5A || hsrc[DV_G + n + i] != 0x5A;
-    if (!bad && n && memcmp(hsrc + DV_G, data, n)) bad = 1;
+    hipStreamSynchronize(user);                          /* (a call refused up front never touched the caller's stream: the uploads may still be queued) */
+    if (region_fetch(&dst) || region_fetch_same(&src, data)) bad = 1;
     if (!bad && want == (size_t)0 && r != t) bad = 2;
-    if (!bad && want != (size_t)0 && (r != want || (want != FERR(GENERIC) && t != want))) bad = 2;
-    if (!bad && !LizardF_isError(r) && memcmp(hdst + DV_G, twin, r)) bad = 3;
-    hipFree(dsrc); hipFree(ddst); hipHostFree(hsrc); hipHostFree(hdst); free(twin);
+    if (!bad && want != (size_t)0 && (r != want || (want != LZ_FRAME_E(GENERIC) && t != want))) bad = 2;
+    if (!bad && !LizardF_isError(r) && memcmp(region_bytes(&dst), twin, r)) bad = 3;
+    region_free(&src); region_free(&dst); free(twin);
     CHECK(!bad, "compressFrame_device: %s (result %zu, twin %zu, wanted %zu; n %zu level %d checksum %d csize %d cap %zu): %s",
           bad == 1 ? "a canary margin or the source changed" : bad == 2 ? "unexpected result" : "frame bytes differ from the twin's",
           r, t, want, n, level, checksum, csize, cap, LizardGPU_lastError());
@@ -136,14 +126,14 @@ int main(void)
             || both(data, 3 * bs + 1, level, 1, checksum, 0, 0, (size_t)0) || both(data, 0, level, 0, checksum, 1, 0, (size_t)0)
             || both(data, 1, level, 0, checksum, 0, 0, (size_t)0)) return 1;
         /* capacity: below the bound; the 1-byte last block at exactly the bound under a content-size header, alone and behind a raw block */
-        if (both(data, n, level, 1, checksum, 1, -1, FERR(dstMaxSize_tooSmall)) || both(data, 1, level, 0, 0, 1, 0, FERR(dstMaxSize_tooSmall))
-            || both(data + 2 * bs, bs + 1, level, 1, 0, 1, 0, FERR(dstMaxSize_tooSmall)) || both(data + 2 * bs, bs + 1, level, 1, 0, 1, 1, (size_t)0)) return 1;
+        if (both(data, n, level, 1, checksum, 1, -1, LZ_FRAME_E(dstMaxSize_tooSmall)) || both(data, 1, level, 0, 0, 1, 0, LZ_FRAME_E(dstMaxSize_tooSmall))
+            || both(data + 2 * bs, bs + 1, level, 1, 0, 1, 0, LZ_FRAME_E(dstMaxSize_tooSmall)) || both(data + 2 * bs, bs + 1, level, 1, 0, 1, 1, (size_t)0)) return 1;
         /* a refused launch, a failing allocation (fresh stages: the first hipMalloc of the call); then a good call */
         pf_refuse_frame_pack(s & 1 ? 2 : 1);
-        if (both(data, n, level, 1, checksum, 0, 0, FERR(GENERIC))) return 1;
+        if (both(data, n, level, 1, checksum, 0, 0, LZ_FRAME_E(GENERIC))) return 1;
         pf_shutdown();
         g_failMalloc = 1 + (int)(s % 3);
-        if (both(data, n, level, 1, checksum, 0, 0, FERR(GENERIC))) return 1;
+        if (both(data, n, level, 1, checksum, 0, 0, LZ_FRAME_E(GENERIC))) return 1;
         if (both(data, n, level, 1, checksum, 0, 0, (size_t)0)) return 1;
     }
     unsetenv("LIZARDGPU_FRAME_CHUNK_BLOCKS");

@@ -16,12 +16,10 @@
 #include <string.h>
 
 #include "../lizard_amd/csrc/lizard_frames_device.c"       /* unit under test, compiled into this harness */
-#include "../lizard_amd/csrc/lizard_xxhash.h"
-#include "fake_hip.h"
+#include "device_fake_common.h"
 #include "lizard_oracle.h"
 
-static int g_refusePack;
-void pf_refuse_frames_pack(int nth) { LzGuard g; lzk_guard_acquire(&g); g_refusePack = nth; lzk_guard_release(&g); }
+void pf_refuse_frames_pack(int nth) { dfc_refuse_set(0, nth); }
 
 /* ---- lz_frames_scan_kernel + lz_frames_gather_kernel: block after block, each frame's cursor advancing as its records are placed ---- */
 typedef struct { const uint8_t* base; const uint64_t* blkOffsets; const uint32_t *blkSizes, *blkFrames; const uint8_t* slots; size_t slot;
@@ -62,34 +60,14 @@ int lzk_frames_pack_launch(const void* d_base, const uint64_t* d_blkOffsets, con
     if (!d_base || !d_blkOffsets || !d_blkSizes || !d_blkFrames || !d_slots || !d_sizes || !d_offsets || !d_frames || nb == 0) {
         snprintf(lzk_err(), LZK_ERR_BYTES, "lzk_frames_pack_launch: bad argument"); return -LIZARDGPU_ERR_ARG;
     }
-    if (g_refusePack && !--g_refusePack) { snprintf(lzk_err(), LZK_ERR_BYTES, "lzk_frames_pack_launch: refused by the test"); return -LIZARDGPU_ERR_HIP; }
+    if (dfc_refused(0, "lzk_frames_pack_launch")) return -LIZARDGPU_ERR_HIP;
     k.base = (const uint8_t*)d_base; k.blkOffsets = d_blkOffsets; k.blkSizes = d_blkSizes; k.blkFrames = d_blkFrames; k.slots = (const uint8_t*)d_slots;
     k.slot = slot; k.sizes = d_sizes; k.offsets = d_offsets; k.nb = nb; k.frames = d_frames;
     return fh_enqueue_kernel(stream, frames_pack_kernel, &k, sizeof k) == hipSuccess ? 0 : -LIZARDGPU_ERR_HIP;
 }
 
 /* ---- lz_xxh32_frames_kernel ---- */
-typedef struct { LzFramesEntry* frames; uint32_t n; } FramesHashK;
-static void frames_hash_kernel(void* a)
-{
-    const FramesHashK* k = (const FramesHashK*)a;
-    const uint32_t want = LZK_FRAMES_LIVE | LZK_FRAMES_CHECKSUM;
-    uint32_t f;
-    if (!fh_check_dev(k->frames, (size_t)k->n * sizeof *k->frames, "frames hash: the frame table")) return;
-    for (f = 0; f < k->n; f++) {
-        LzFramesEntry* e = k->frames + f;
-        if ((e->flags & want) != want) continue;
-        if (e->srcSize && !fh_check_dev((const void*)(uintptr_t)e->src, (size_t)e->srcSize, "frames hash: a frame's source")) continue;
-        e->hash = Lizard_XXH32((const void*)(uintptr_t)e->src, (size_t)e->srcSize, 0);
-    }
-}
-int lzk_frames_hash_launch(LzFramesEntry* d_frames, uint32_t nFrames, hipStream_t stream)
-{
-    FramesHashK k;
-    if (!d_frames || nFrames == 0) { snprintf(lzk_err(), LZK_ERR_BYTES, "lzk_frames_hash_launch: bad argument"); return -LIZARDGPU_ERR_ARG; }
-    k.frames = d_frames; k.n = nFrames;
-    return fh_enqueue_kernel(stream, frames_hash_kernel, &k, sizeof k) == hipSuccess ? 0 : -LIZARDGPU_ERR_HIP;
-}
+int lzk_frames_hash_launch(LzFramesEntry* d_frames, uint32_t nFrames, hipStream_t stream) { return dfc_frames_hash_launch(d_frames, nFrames, stream); }
 
 /* ---- lz_frames_finish_kernel ---- */
 typedef struct { const LzFramesEntry* frames; LzFramesResult* results; uint32_t n; } FramesFinishK;
@@ -130,16 +108,12 @@ int lzk_frames_finish_launch(const LzFramesEntry* d_frames, LzFramesResult* d_re
 /* ---- one batch against the host twin, frame by frame ---- */
 void pf_set_chunk_bytes(size_t n);
 void pf_shutdown(void);
-#define CHECK(cond, ...) do { if (!(cond)) { fprintf(stderr, "frames_device_fake: line %d: ", __LINE__); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); return 1; } } while (0)
-#define FERR(code) ((size_t)-(long)(LIZARDGPU_FRAME_ERR_##code))
-#define FDF_G 4096
+#define CHECK(cond, ...) DFC_CHECK("frames_device_fake", cond, __VA_ARGS__)
 #define FDF_MAX 16
 #define FDF_BLOCK ((size_t)131072)
 #define FDF_DATA (12 * FDF_BLOCK)
-static hipStream_t g_user;
 static uint8_t* g_data;
-static char g_text[LZK_ERR_BYTES];
-const char* fdf_last_error(void) { return g_text; }            /* LizardGPU_lastError as the last batch left it (the twins' calls come behind it) */
+const char* fdf_last_error(void) { return dfc_text; }            /* LizardGPU_lastError as the last batch left it (the twins' calls come behind it) */
 
 /* P50 with noise across block borders, so that raw records lie between compressed ones */
 static const uint8_t* fdf_data(void)
@@ -165,7 +139,8 @@ int fdf_batch(size_t nf, const size_t* offs, const size_t* sizes, const long* ca
 {
     const uint8_t* const data = fdf_data();
     LizardF_preferences_t p;
-    uint8_t *dsrc[FDF_MAX], *ddst[FDF_MAX], *hsrc[FDF_MAX], *hdst[FDF_MAX];
+    const hipStream_t user = dfc_user();
+    Region src[FDF_MAX], dst[FDF_MAX];
     void* dsts[FDF_MAX]; const void* srcs[FDF_MAX];
     size_t caps[FDF_MAX], results[FDF_MAX], i, g;
     unsigned long long s0[4], s1[4];
@@ -174,51 +149,42 @@ int fdf_batch(size_t nf, const size_t* offs, const size_t* sizes, const long* ca
     memset(&p, 0, sizeof p);
     p.frameInfo.blockSizeID = (LizardF_blockSizeID_t)bsid; p.frameInfo.blockMode = (LizardF_blockMode_t)1;
     p.frameInfo.contentChecksumFlag = (LizardF_contentChecksum_t)checksum; p.compressionLevel = level;
-    if (!g_user) hipStreamCreateWithFlags(&g_user, hipStreamNonBlocking);
     for (i = 0; i < nf; i++) {
-        const size_t n = sizes[i], sn = n + 2 * FDF_G + 4, skew = i % 4;
-        size_t dn;
+        const size_t n = sizes[i];
         CHECK(offs[i] + n <= FDF_DATA, "a frame outside the data");
         p.frameInfo.contentSize = csize ? n : 0;
-        caps[i] = (size_t)((long)LizardGPU_compressFrameBound(n, &p) + capDeltas[i]); dn = caps[i] + 2 * FDF_G;
-        CHECK(hipMalloc((void**)&dsrc[i], sn) == hipSuccess && hipMalloc((void**)&ddst[i], dn) == hipSuccess
-              && hipHostMalloc((void**)&hsrc[i], sn, 0) == hipSuccess && hipHostMalloc((void**)&hdst[i], dn, 0) == hipSuccess, "allocation");
-        memset(hsrc[i], 0x5A, sn); if (n) memcpy(hsrc[i] + FDF_G + skew, data + offs[i], n);
-        memset(hdst[i], 0xC3, dn);
-        hipMemcpyAsync(dsrc[i], hsrc[i], sn, hipMemcpyHostToDevice, g_user); hipMemcpyAsync(ddst[i], hdst[i], dn, hipMemcpyHostToDevice, g_user);
-        srcs[i] = dsrc[i] + FDF_G + skew; dsts[i] = ddst[i] + FDF_G; results[i] = 12345;
+        caps[i] = (size_t)((long)LizardGPU_compressFrameBound(n, &p) + capDeltas[i]);
+        CHECK(!region_make(&src[i], data + offs[i], n, i % 4, 0x5A) && !region_make(&dst[i], NULL, caps[i], 0, 0xC3), "allocation");
+        srcs[i] = region_at(&src[i]); dsts[i] = region_at(&dst[i]); results[i] = 12345;
     }
     p.frameInfo.contentSize = csize ? 1 : 0;                /* (not zero: every frame writes its own size) */
-    if (failMalloc) hipStreamSynchronize(g_user);          /* (a call that fails before it orders itself behind the caller's stream leaves that stream's work queued, as it may) */
+    if (failMalloc) hipStreamSynchronize(user);          /* (a call that fails before it orders itself behind the caller's stream leaves that stream's work queued, as it may) */
     memcpy(s0, lzk_ctx_peek()->devFrameCompressStats, sizeof s0);      /* (what LizardGPU_frameCompressDeviceStats of lizard_frame_device.c reads) */
     fh_fail_malloc(failMalloc);
-    rc = LizardGPU_compressFrames_device(nf, dsts, caps, srcs, sizes, results, &p, g_user);
+    rc = LizardGPU_compressFrames_device(nf, dsts, caps, srcs, sizes, results, &p, user);
     fh_fail_malloc(0);
-    snprintf(g_text, sizeof g_text, "%s", LizardGPU_lastError());
+    dfc_keep_text();
     memcpy(s1, lzk_ctx_peek()->devFrameCompressStats, sizeof s1);
     for (g = 0; g < 4 && grown; g++) grown[g] = s1[g] - s0[g];
-    hipStreamSynchronize(g_user);                          /* (a call that refused every frame up front never touched the caller's stream) */
+    hipStreamSynchronize(user);                          /* (a call that refused every frame up front never touched the caller's stream) */
     for (i = 0; i < nf && !bad; i++) {
-        const size_t n = sizes[i], sn = n + 2 * FDF_G + 4, dn = caps[i] + 2 * FDF_G, skew = i % 4;
+        const size_t n = sizes[i];
         uint8_t* twin = (uint8_t*)malloc(caps[i] + 1);
         size_t t, q;
         p.frameInfo.contentSize = csize ? n : 0;
         t = LizardGPU_compressFrame(twin, caps[i], data + offs[i], n, &p);
-        memset(hdst[i], 0, dn); memset(hsrc[i], 0, sn);
-        hipMemcpy(hdst[i], ddst[i], dn, hipMemcpyDeviceToHost); hipMemcpy(hsrc[i], dsrc[i], sn, hipMemcpyDeviceToHost);
-        for (q = 0; q < FDF_G; q++) bad |= hdst[i][q] != 0xC3 || hdst[i][FDF_G + caps[i] + q] != 0xC3 || hsrc[i][q] != 0x5A || hsrc[i][FDF_G + skew + n + q] != 0x5A;
-        if (!bad && n && memcmp(hsrc[i] + FDF_G + skew, data + offs[i], n)) bad = 1;
-        if (!bad && (wantRc ? results[i] != FERR(GENERIC) : results[i] != t)) bad = 2;
-        if (!bad && !wantRc && !LizardF_isError(t) && memcmp(hdst[i] + FDF_G, twin, t)) bad = 3;
-        if (!bad && !wantRc && capDeltas[i] < 0) for (q = 0; q < caps[i]; q++) if (hdst[i][FDF_G + q] != 0xC3) bad = 4;
+        if (region_fetch(&dst[i]) || region_fetch_same(&src[i], data + offs[i])) bad = 1;
+        if (!bad && (wantRc ? results[i] != LZ_FRAME_E(GENERIC) : results[i] != t)) bad = 2;
+        if (!bad && !wantRc && !LizardF_isError(t) && memcmp(region_bytes(&dst[i]), twin, t)) bad = 3;
+        if (!bad && !wantRc && capDeltas[i] < 0) for (q = 0; q < caps[i]; q++) if (region_bytes(&dst[i])[q] != 0xC3) bad = 4;
         free(twin);
         if (bad) fprintf(stderr, "frames_device_fake: frame %zu of %zu: %s (result %zu, twin %zu; n %zu level %d checksum %d csize %d cap %zu; call returned %d): %s\n", i, nf,
                          bad == 1 ? "a canary margin or the source changed" : bad == 2 ? "unexpected result" : bad == 3 ? "frame bytes differ from the twin's"
-                         : "a frame refused below its bound was written to", results[i], t, n, level, checksum, csize, caps[i], rc, g_text);
+                         : "a frame refused below its bound was written to", results[i], t, n, level, checksum, csize, caps[i], rc, dfc_text);
     }
-    for (i = 0; i < nf; i++) { hipFree(dsrc[i]); hipFree(ddst[i]); hipHostFree(hsrc[i]); hipHostFree(hdst[i]); }
+    for (i = 0; i < nf; i++) { region_free(&src[i]); region_free(&dst[i]); }
     CHECK(!bad, "a frame of the batch is wrong");
-    CHECK(rc == wantRc, "the call returned %d, wanted %d: %s", rc, wantRc, g_text);
+    CHECK(rc == wantRc, "the call returned %d, wanted %d: %s", rc, wantRc, dfc_text);
     return 0;
 }
 

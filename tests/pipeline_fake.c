@@ -23,7 +23,7 @@
 #include "../lizard_amd/csrc/lizard_unframe_host.c"
 #undef LZ_HIP
 #include "../lizard_amd/csrc/lizard_unframe_device.c"     /* (its statics are v_* / LZV_*, the host twin's uf_* / LZU_*) */
-#include "fake_hip.h"
+#include "device_fake_common.h"
 #include "lizard_oracle.h"
 
 unsigned emul_unframe_record(const void* payload, unsigned size, unsigned word, void* slot, unsigned cap, unsigned seed);
@@ -69,12 +69,6 @@ void lzgpu_note_degraded(const char* what, int level) { (void)what; (void)level;
 
 /* lz_unframe_kernel: one wave per record, in whatever order the waves claim them */
 typedef struct { const uint8_t* src; const uint64_t* offs; const uint32_t* words; size_t n; uint8_t* slots; size_t slotBytes; uint32_t *outSizes, *packSizes; } UnframeK;
-static void shuffled(uint32_t* order, size_t n)
-{
-    size_t i;
-    for (i = 0; i < n; i++) order[i] = (uint32_t)i;
-    for (i = n; i > 1; i--) { const size_t k = fh_rand() % i; const uint32_t t = order[i - 1]; order[i - 1] = order[k]; order[k] = t; }
-}
 static void unframe_kernel(void* a)
 {
     const UnframeK* k = (const UnframeK*)a;
@@ -84,7 +78,7 @@ static void unframe_kernel(void* a)
     if (!fh_check_dev(k->offs, 8 * k->n, "unframe: payload offsets") || !fh_check_dev(k->words, 4 * k->n, "unframe: words")
         || !fh_check_dev(k->outSizes, 4 * k->n, "unframe: outSizes") || !fh_check_dev(k->packSizes, 4 * k->n, "unframe: packSizes")
         || !fh_check_dev(k->slots, k->n * k->slotBytes, "unframe: slots")) { free(order); return; }
-    shuffled(order, k->n);
+    dfc_shuffled(order, k->n);
     for (i = 0; i < k->n; i++) {
         const uint32_t b = order[i], word = k->words[b], size = word & 0x7FFFFFFFu;
         uint32_t r;
@@ -116,7 +110,7 @@ static void inplace_kernel(void* a)
     if (!fh_check_dev(k->offs, 8 * k->n, "inplace: payload offsets") || !fh_check_dev(k->words, 4 * k->n, "inplace: words")
         || !fh_check_dev(k->outSizes, 4 * k->n, "inplace: outSizes") || !fh_check_dev(k->packSizes, 4 * k->n, "inplace: packSizes")
         || !fh_check_dev(k->dst, k->dstRoom, "inplace: dst[0..dstRoom)")) { free(order); return; }
-    shuffled(order, k->n);
+    dfc_shuffled(order, k->n);
     for (i = 0; i < k->n; i++) {
         const uint32_t b = order[i], word = k->words[b], size = word & 0x7FFFFFFFu;
         const size_t at = (size_t)b * k->slotBytes;
@@ -177,7 +171,7 @@ static void decompress_kernel(void* a)
     size_t i;
     if ((k->offs && !fh_check_dev(k->offs, 8 * (k->n + 1), "decompress: offsets")) || (!k->offs && !fh_check_dev(k->srcSizes, 4 * k->n, "decompress: sizes"))
         || !fh_check_dev(k->outSizes, 4 * k->n, "decompress: outSizes") || !fh_check_dev(k->dst, k->n * k->dstStride, "decompress: slots")) { free(order); return; }
-    shuffled(order, k->n);
+    dfc_shuffled(order, k->n);
     for (i = 0; i < k->n; i++) {
         const uint32_t b = order[i];
         const uint8_t* in = k->offs ? k->src + k->offs[b] : k->src + (size_t)b * k->srcStride;
@@ -207,7 +201,7 @@ static void compress_kernel(void* a)
     size_t i;
     if (!fh_check_dev(k->sizes, 4 * k->nb, "compress: sizes") || !fh_check_dev(k->dst, k->nb * k->stride, "compress: slots")
         || (k->srcSizes && (!fh_check_dev(k->srcSizes, 4 * k->nb, "compress: srcSizes") || !fh_check_dev(k->srcOffsets, 8 * k->nb, "compress: srcOffsets")))) { free(order); return; }
-    shuffled(order, k->nb);
+    dfc_shuffled(order, k->nb);
     for (i = 0; i < k->nb; i++) {
         const size_t b = order[i];
         const size_t n = k->srcSizes ? k->srcSizes[b] : (b + 1 == k->nb ? k->last : k->blockSize);
@@ -302,8 +296,7 @@ void pf_shutdown(void)
 
 #ifdef PIPELINE_FAKE_MAIN
 /* ---- the program form: core cases and the thread test, for the sanitizer builds ---- */
-#define CHECK(cond, ...) do { if (!(cond)) { fprintf(stderr, "pipeline_fake: line %d: ", __LINE__); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); return 1; } } while (0)
-#define FERR(code) ((size_t)-(long)(LIZARDGPU_FRAME_ERR_##code))
+#define CHECK(cond, ...) DFC_CHECK("pipeline_fake", cond, __VA_ARGS__)
 typedef struct { uint8_t* frame; size_t bytes; const uint8_t* plain; size_t n; } Frame;
 static uint8_t *g_data, *g_noise;
 static size_t g_n, g_noiseN;
@@ -347,7 +340,7 @@ static int decode_check(const Frame* f, int pinned, uint8_t* out /* f->n + 64 */
     CHECK(r == f->n && used == f->bytes, "decompressFrame returned %zu (consumed %zu) for %zu bytes: %s", r, used, f->n, LizardGPU_lastError());
     CHECK(!memcmp(out, f->plain, f->n) && out[f->n] == 0xC3, "decoded bytes differ");
     r = LizardGPU_decompressFrame(out, f->n - 1, src + 3, f->bytes, &used);
-    CHECK(r == FERR(dstMaxSize_tooSmall) && used == 0, "capacity n - 1: %zu", r);
+    CHECK(r == LZ_FRAME_E(dstMaxSize_tooSmall) && used == 0, "capacity n - 1: %zu", r);
     if (pinned) fh_unregister_pinned(src);
     free(src);
     return 0;
@@ -501,7 +494,7 @@ static int dev_check(const Frame* f)
 {
     if (dev_decode(f, f->n, 0, f->n, 1)) return 1;
     if (dev_decode(f, f->n + 77, 1u, f->n, 1)) return 1;
-    return dev_decode(f, f->n - 1, 0, FERR(dstMaxSize_tooSmall), 0);
+    return dev_decode(f, f->n - 1, 0, LZ_FRAME_E(dstMaxSize_tooSmall), 0);
 }
 static int devcore(void)
 {
@@ -521,19 +514,19 @@ static int devcore(void)
         for (f = 0; f < g_nFrames; f++)
             if (dev_check(&g_frames[f])) { fprintf(stderr, "  (frame %d, schedule %d seed %u)\n", f, sched[s].mode, sched[s].seed); return 1; }
         /* capacity edges: a slot border with records to come, inside a slot, nothing */
-        if (dev_decode(&g_frames[0], 2 * 131072, 0, FERR(dstMaxSize_tooSmall), 0) || dev_decode(&g_frames[0], 3 * 131072 + 100, 0, FERR(dstMaxSize_tooSmall), 0)
-            || dev_decode(&g_frames[0], 0, 0, FERR(dstMaxSize_tooSmall), 0)) return 1;
+        if (dev_decode(&g_frames[0], 2 * 131072, 0, LZ_FRAME_E(dstMaxSize_tooSmall), 0) || dev_decode(&g_frames[0], 3 * 131072 + 100, 0, LZ_FRAME_E(dstMaxSize_tooSmall), 0)
+            || dev_decode(&g_frames[0], 0, 0, LZ_FRAME_E(dstMaxSize_tooSmall), 0)) return 1;
         /* a damaged record, a frame cut inside its checksum, a stored checksum that is wrong (and skipped), a launch that is refused */
         bad.frame = (uint8_t*)malloc(bad.bytes); memcpy(bad.frame, g_frames[0].frame, bad.bytes);
         memset(bad.frame + bad.bytes / 2, 0xFF, 40);
         if (dev_decode(&bad, g_n, 0, 0, 2)) return 1;
         memcpy(bad.frame, g_frames[0].frame, bad.bytes); bad.frame[bad.bytes - 1] ^= 1;
-        if (dev_decode(&bad, g_n, 0, FERR(contentChecksum_invalid), 0) || dev_decode(&bad, g_n, 1u, g_n, 1)) return 1;
+        if (dev_decode(&bad, g_n, 0, LZ_FRAME_E(contentChecksum_invalid), 0) || dev_decode(&bad, g_n, 1u, g_n, 1)) return 1;
         free(bad.frame);
         cut.bytes -= 2;
-        if (dev_decode(&cut, g_n, 0, FERR(GENERIC), 0)) return 1;
+        if (dev_decode(&cut, g_n, 0, LZ_FRAME_E(GENERIC), 0)) return 1;
         pf_refuse_launch((int)(s & 1), s ? 2 : 1);           /* the walk or the in-place launch, of the first or the second segment */
-        if (dev_decode(&g_frames[2], g_n, 0, FERR(GENERIC), 0)) return 1;
+        if (dev_decode(&g_frames[2], g_n, 0, LZ_FRAME_E(GENERIC), 0)) return 1;
         if (dev_check(&g_frames[2]) || decode_check(&g_frames[1], (int)(s & 1), out)) return 1;
     }
     unsetenv("LIZARDGPU_WALK_RECORDS");

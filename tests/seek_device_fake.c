@@ -13,7 +13,7 @@
 #include <string.h>
 
 #include "../lizard_amd/csrc/lizard_seek_device.c"            /* unit under test, compiled into this harness */
-#include "fake_hip.h"
+#include "device_fake_common.h"
 
 size_t lzgpu_stream_compress(void* d_dst, size_t dstCapacity, size_t nFrames, const void* const* d_srcs, const size_t* srcSizes,
                              const void* const* prefixes, const size_t* prefixSizes, const LizardGPU_framePrefs_t* prefs, uint64_t* frameOffsets,
@@ -32,34 +32,7 @@ int lzk_stream_seektable_launch(const LzFramesEntry* d_frames, const LzStreamEnt
     return -LIZARDGPU_ERR_HIP;
 }
 
-#define SSF_G 4096
-static hipStream_t g_user;
-static char g_text[LZK_ERR_BYTES];
-const char* ssf_last_error(void) { return g_text; }           /* LizardGPU_lastError as the seekable entry left it */
-
-/* a device region of n bytes from `bytes` (or of `fill`), skew bytes off the 4 KiB margin, uploaded on the caller's stream, not waited for */
-typedef struct { uint8_t *dev, *host; size_t n, skew; uint8_t fill; } Region;
-static int region_make(Region* r, const uint8_t* bytes, size_t n, size_t skew, uint8_t fill)
-{
-    const size_t all = n + 2 * SSF_G + 8;
-    r->n = n; r->skew = skew; r->fill = fill;
-    if (hipMalloc((void**)&r->dev, all) != hipSuccess || hipHostMalloc((void**)&r->host, all, 0) != hipSuccess) return 1;
-    memset(r->host, fill, all);
-    if (bytes && n) memcpy(r->host + SSF_G + skew, bytes, n);
-    return hipMemcpyAsync(r->dev, r->host, all, hipMemcpyHostToDevice, g_user) != hipSuccess;
-}
-static uint8_t* region_at(const Region* r) { return r->dev + SSF_G + r->skew; }
-static int region_fetch(Region* r)                             /* downloads; 0 when the margins hold `fill` */
-{
-    const size_t all = r->n + 2 * SSF_G + 8;
-    size_t q;
-    memset(r->host, 0, all);
-    if (hipMemcpy(r->host, r->dev, all, hipMemcpyDeviceToHost) != hipSuccess) return 1;
-    for (q = 0; q < SSF_G + r->skew; q++) if (r->host[q] != r->fill) return 1;
-    for (q = SSF_G + r->skew + r->n; q < all; q++) if (r->host[q] != r->fill) return 1;
-    return 0;
-}
-static void region_free(Region* r) { hipFree(r->dev); hipHostFree(r->host); }
+const char* ssf_last_error(void) { return dfc_text; }           /* LizardGPU_lastError as the seekable entry left it */
 
 /* The stream `bytes` through LizardGPU_decompressStream_device and through LizardGPU_decompressSeekableStream_device, cap bytes of room
  * each.  0 when the two answers are one; got: the seekable entry's return value, consumed, frames, decoded, then the growth of
@@ -69,22 +42,22 @@ int ssf_run(const uint8_t* bytes, size_t n, size_t cap, unsigned flags, unsigned
     Region src, a, b;
     unsigned long long s0[4], s1[4];
     size_t ra, rb, ua = 111, ub = 222, fa = 111, fb = 222, da = 111, db = 222;
+    const hipStream_t user = dfc_user();
     int bad = 0, g;
-    if (!g_user) hipStreamCreateWithFlags(&g_user, hipStreamNonBlocking);
     if (region_make(&src, bytes, n, skew & 7, 0x5A) || region_make(&a, NULL, cap, (skew * 3) & 7, 0xC3) || region_make(&b, NULL, cap, (skew * 5) & 7, 0xC3)) return 100;
-    ra = LizardGPU_decompressStream_device(region_at(&a), cap, region_at(&src), n, &ua, &fa, &da, flags, g_user);
+    ra = LizardGPU_decompressStream_device(region_at(&a), cap, region_at(&src), n, &ua, &fa, &da, flags, user);
     LizardGPU_seekDeviceStats(s0);
-    rb = LizardGPU_decompressSeekableStream_device(region_at(&b), cap, region_at(&src), n, &ub, &fb, &db, flags, g_user);
-    snprintf(g_text, sizeof g_text, "%s", LizardGPU_lastError());
+    rb = LizardGPU_decompressSeekableStream_device(region_at(&b), cap, region_at(&src), n, &ub, &fb, &db, flags, user);
+    dfc_keep_text();
     LizardGPU_seekDeviceStats(s1);
-    hipStreamSynchronize(g_user);
+    hipStreamSynchronize(user);
     if (got) { got[0] = rb; got[1] = ub; got[2] = fb; got[3] = db; for (g = 0; g < 4; g++) got[4 + g] = s1[g] - s0[g]; }
-    if (region_fetch(&src) || region_fetch(&a) || region_fetch(&b) || (n && memcmp(src.host + SSF_G + src.skew, bytes, n))) bad = 1;
+    if (region_fetch_same(&src, bytes) || region_fetch(&a) || region_fetch(&b)) bad = 1;
     if (!bad && (ra != rb || ua != ub || fa != fb || da != db)) bad = 2;
-    if (!bad && da && memcmp(a.host + SSF_G + a.skew, b.host + SSF_G + b.skew, da)) bad = 3;
+    if (!bad && da && memcmp(region_bytes(&a), region_bytes(&b), da)) bad = 3;
     if (bad) fprintf(stderr, "seek_device_fake: %s (walk: %zu, consumed %zu, %zu frames, %zu decoded; seekable: %zu, consumed %zu, %zu frames, %zu decoded; %zu bytes, cap %zu): %s\n",
                      bad == 1 ? "a canary margin or the source changed" : bad == 2 ? "the answers differ" : "the decoded bytes differ", ra, ua, fa, da, rb, ub, fb,
-                     db, n, cap, g_text);
+                     db, n, cap, dfc_text);
     region_free(&src); region_free(&a); region_free(&b);
     return bad;
 }
@@ -93,14 +66,14 @@ int ssf_run(const uint8_t* bytes, size_t n, size_t cap, unsigned flags, unsigned
 size_t ssf_items(const uint8_t* bytes, size_t n, size_t cap, const size_t* items, size_t nItems, uint64_t* itemOffsets, size_t* failedItem, uint8_t* out)
 {
     Region src, d;
+    const hipStream_t user = dfc_user();
     size_t r;
-    if (!g_user) hipStreamCreateWithFlags(&g_user, hipStreamNonBlocking);
     if (region_make(&src, bytes, n, 3, 0x5A) || region_make(&d, NULL, cap, 5, 0xC3)) return LZ_FRAME_E(allocation_failed);
-    r = LizardGPU_decompressStreamItems_device(region_at(&d), cap, region_at(&src), n, items, nItems, itemOffsets, failedItem, 0, g_user);
-    snprintf(g_text, sizeof g_text, "%s", LizardGPU_lastError());
-    hipStreamSynchronize(g_user);
+    r = LizardGPU_decompressStreamItems_device(region_at(&d), cap, region_at(&src), n, items, nItems, itemOffsets, failedItem, 0, user);
+    dfc_keep_text();
+    hipStreamSynchronize(user);
     if (region_fetch(&src) || region_fetch(&d)) r = LZ_FRAME_E(maxCode);
-    else if (cap) memcpy(out, d.host + SSF_G + d.skew, cap);
+    else if (cap) memcpy(out, region_bytes(&d), cap);
     region_free(&src); region_free(&d);
     return r;
 }

@@ -17,7 +17,7 @@
 #include <string.h>
 
 #include "../lizard_amd/csrc/lizard_slice_device.c"          /* unit under test, compiled into this harness */
-#include "fake_hip.h"
+#include "device_fake_common.h"
 #include "lizard_oracle.h"
 
 unsigned emul_unframe_record(const void* payload, unsigned size, unsigned word, void* slot, unsigned cap, unsigned seed);      /* tests/pipeline_fake_emul.cpp */
@@ -34,8 +34,7 @@ static void unslice_kernel(void* a)
     size_t i;
     if (!fh_check_dev(k->picks, k->n * sizeof *k->picks, "unslice: the picks") || !fh_check_dev(k->out, 4 * k->n, "unslice: results")) return;
     order = (uint32_t*)malloc(k->n * sizeof *order);
-    for (i = 0; i < k->n; i++) order[i] = (uint32_t)i;
-    for (i = k->n; i > 1; i--) { const size_t s = fh_rand() % i; const uint32_t t = order[i - 1]; order[i - 1] = order[s]; order[s] = t; }
+    dfc_shuffled(order, k->n);
     for (i = 0; i < k->n; i++) {
         const uint32_t b = order[i];
         const LzSlicePick* p = k->picks + b;
@@ -104,40 +103,12 @@ int lzk_planes_range_launch(LzCtx* c, const LzPlanesRangeEntry* d_tab, uint32_t 
 
 /* ---- one call against the full decode, range by range ---- */
 void pf_shutdown(void);
-#define CHECK(cond, ...) do { if (!(cond)) { fprintf(stderr, "slice_device_fake: line %d: ", __LINE__); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); return 1; } } while (0)
-#define FERR(code) ((size_t)-(long)(LIZARDGPU_FRAME_ERR_##code))
-#define SDF_G 4096
+#define CHECK(cond, ...) DFC_CHECK("slice_device_fake", cond, __VA_ARGS__)
 #define SDF_MAX 16
 #define SDF_BLOCK ((size_t)131072)
 #define SDF_DATA (12 * SDF_BLOCK)
-static hipStream_t g_user;
 static uint8_t* g_data;
-static char g_text[LZK_ERR_BYTES];
-const char* sdf_last_error(void) { return g_text; }
-
-typedef struct { uint8_t *dev, *host; size_t n, skew; uint8_t fill; } Region;
-static int region_make(Region* r, const uint8_t* bytes, size_t n, size_t skew, uint8_t fill)
-{
-    const size_t all = n + 2 * SDF_G + 4;
-    r->n = n; r->skew = skew; r->fill = fill;
-    if (hipMalloc((void**)&r->dev, all) != hipSuccess || hipHostMalloc((void**)&r->host, all, 0) != hipSuccess) return 1;
-    memset(r->host, fill, all);
-    if (bytes && n) memcpy(r->host + SDF_G + skew, bytes, n);
-    return hipMemcpyAsync(r->dev, r->host, all, hipMemcpyHostToDevice, g_user) != hipSuccess;
-}
-static uint8_t* region_at(const Region* r) { return r->dev + SDF_G + r->skew; }
-/* downloads; 0 when the margins hold `fill`; the region's bytes are at host + SDF_G + skew then */
-static int region_fetch(Region* r)
-{
-    const size_t all = r->n + 2 * SDF_G + 4;
-    size_t q;
-    memset(r->host, 0, all);
-    if (hipMemcpy(r->host, r->dev, all, hipMemcpyDeviceToHost) != hipSuccess) return 1;
-    for (q = 0; q < SDF_G + r->skew; q++) if (r->host[q] != r->fill) return 1;
-    for (q = SDF_G + r->skew + r->n; q < all; q++) if (r->host[q] != r->fill) return 1;
-    return 0;
-}
-static void region_free(Region* r) { hipFree(r->dev); hipHostFree(r->host); }
+const char* sdf_last_error(void) { return dfc_text; }
 
 /* Frame i: sizes[i] bytes at frames[i] (host memory) with ranges [firstRange[i], + nRanges[i]) of `ranges` (nr of them, lo and hi in
  * turn); the destination has `cap` bytes.  Out: results[nf], rangeAt[nr + 1], grown[4] (LizardGPU_sliceDeviceStats over the call),
@@ -152,10 +123,10 @@ int sdf_run(size_t nf, const uint8_t* const* frames, const size_t* sizes, const 
     LizardGPU_sliceFrame_t fr[SDF_MAX];
     unsigned long long s0[4], s1[4];
     size_t i, g, q;
+    const hipStream_t user = dfc_user();
     int rc, bad = 0;
     (void)nr;
     CHECK(nf <= SDF_MAX, "too many frames");
-    if (!g_user) hipStreamCreateWithFlags(&g_user, hipStreamNonBlocking);
     for (i = 0; i < nf; i++) {
         CHECK(!region_make(&src[i], frames[i], sizes[i], i % 4, 0x5A), "allocation");
         fr[i].d_src = region_at(&src[i]); fr[i].srcSize = sizes[i]; fr[i].firstRange = firstRange[i]; fr[i].nRanges = nRanges[i];
@@ -163,26 +134,26 @@ int sdf_run(size_t nf, const uint8_t* const* frames, const size_t* sizes, const 
     }
     CHECK(!region_make(&dst, NULL, cap, 3, 0xC3), "allocation");
     LizardGPU_sliceDeviceStats(s0);
-    rc = LizardGPU_decompressFrameRanges_device(region_at(&dst), cap, nf, fr, (const LizardGPU_byteRange_t*)ranges, rangeAt, results, g_user);
-    snprintf(g_text, sizeof g_text, "%s", LizardGPU_lastError());
+    rc = LizardGPU_decompressFrameRanges_device(region_at(&dst), cap, nf, fr, (const LizardGPU_byteRange_t*)ranges, rangeAt, results, user);
+    dfc_keep_text();
     LizardGPU_sliceDeviceStats(s1);
     for (g = 0; g < 4; g++) grown[g] = s1[g] - s0[g];
     *rcOut = rc;
-    hipStreamSynchronize(g_user);
+    hipStreamSynchronize(user);
     if (region_fetch(&dst)) bad = 1;
-    if (!bad && rc) for (q = 0; q < cap; q++) if (dst.host[SDF_G + dst.skew + q] != 0xC3) { bad = 4; break; }
+    if (!bad && rc) for (q = 0; q < cap; q++) if (region_bytes(&dst)[q] != 0xC3) { bad = 4; break; }
     for (i = 0; i < nf && !bad; i++) {
         const int other = refs && refs[i];
         size_t t, used = 0, room;
         uint32_t r;
-        if (region_fetch(&src[i]) || (sizes[i] && memcmp(src[i].host + SDF_G + src[i].skew, frames[i], sizes[i]))) { bad = 1; break; }
+        if (region_fetch_same(&src[i], frames[i])) { bad = 1; break; }
         if (rc || results[i]) continue;
         room = LizardGPU_decompressFrameBound(other ? refs[i] : frames[i], other ? refSizes[i] : sizes[i]);
         CHECK(!LizardGPU_frameIsError(room), "the bound of a frame the entry answered");
         CHECK(!region_make(&one, NULL, room, 1, 0xC3) && (!other || !region_make(&twin, refs[i], refSizes[i], 2, 0x5A)), "allocation");
         t = LizardGPU_decompressFrame_device(region_at(&one), room, other ? region_at(&twin) : fr[i].d_src, other ? refSizes[i] : sizes[i], &used,
-                                             LIZARDGPU_FRAME_SKIP_CHECKSUM, g_user);
-        hipStreamSynchronize(g_user);
+                                             LIZARDGPU_FRAME_SKIP_CHECKSUM, user);
+        hipStreamSynchronize(user);
         if (region_fetch(&one)) bad = 5;
         if (other) region_free(&twin);
         if (!bad && LizardGPU_frameIsError(t)) bad = 2;
@@ -191,12 +162,12 @@ int sdf_run(size_t nf, const uint8_t* const* frames, const size_t* sizes, const 
             const uint64_t at = rangeAt[firstRange[i] + r] + lo % SDF_BLOCK;
             if (hi <= lo) { if (rangeAt[firstRange[i] + r + 1] != rangeAt[firstRange[i] + r]) bad = 6; continue; }
             if (hi > t || at + (hi - lo) > cap) bad = 3;
-            else if (memcmp(dst.host + SDF_G + dst.skew + at, one.host + SDF_G + one.skew + lo, (size_t)(hi - lo))) bad = 3;
+            else if (memcmp(region_bytes(&dst) + at, region_bytes(&one) + lo, (size_t)(hi - lo))) bad = 3;
         }
         region_free(&one);
         if (bad) fprintf(stderr, "slice_device_fake: frame %zu of %zu: %s (call returned %d): %s\n", i, nf,
                          bad == 2 ? "the single entry refuses a frame the slice entry answered" : bad == 3 ? "a range's bytes differ from the full decode's"
-                         : bad == 6 ? "an empty range takes room" : "the single entry wrote outside its d_dst", rc, g_text);
+                         : bad == 6 ? "an empty range takes room" : "the single entry wrote outside its d_dst", rc, dfc_text);
     }
     if (bad == 1) fprintf(stderr, "slice_device_fake: a canary margin or a source changed\n");
     if (bad == 4) fprintf(stderr, "slice_device_fake: a failed call wrote into d_dst\n");
@@ -223,7 +194,7 @@ static const uint8_t* sdf_data(void)
 size_t sdf_frame(uint8_t* out, size_t cap, size_t off, size_t n, int level, int checksum, int csize)
 {
     LizardF_preferences_t p;
-    if (off + n > SDF_DATA) return FERR(GENERIC);
+    if (off + n > SDF_DATA) return LZ_FRAME_E(GENERIC);
     memset(&p, 0, sizeof p);
     p.frameInfo.blockSizeID = (LizardF_blockSizeID_t)1; p.frameInfo.blockMode = (LizardF_blockMode_t)1;
     p.frameInfo.contentChecksumFlag = (LizardF_contentChecksum_t)checksum; p.frameInfo.contentSize = csize ? n : 0; p.compressionLevel = level;
@@ -237,10 +208,10 @@ size_t sdf_flushed_frame(uint8_t* out, size_t cap, size_t off, size_t head, size
     LizardF_compressionContext_t cctx;
     LizardF_preferences_t p;
     size_t at = 0, r;
-    if (off + n > SDF_DATA || head > n) return FERR(GENERIC);
+    if (off + n > SDF_DATA || head > n) return LZ_FRAME_E(GENERIC);
     memset(&p, 0, sizeof p);
     p.frameInfo.blockSizeID = (LizardF_blockSizeID_t)1; p.frameInfo.blockMode = (LizardF_blockMode_t)1; p.frameInfo.contentSize = n; p.compressionLevel = level;
-    if (LizardF_isError(LizardF_createCompressionContext(&cctx, 100))) return FERR(GENERIC);
+    if (LizardF_isError(LizardF_createCompressionContext(&cctx, 100))) return LZ_FRAME_E(GENERIC);
 #define STEP(call) do { r = (call); if (LizardF_isError(r)) { LizardF_freeCompressionContext(cctx); return r; } at += r; } while (0)
     STEP(LizardF_compressBegin(cctx, out + at, cap - at, &p));
     STEP(LizardF_compressUpdate(cctx, out + at, cap - at, sdf_data() + off, head, NULL));
@@ -262,18 +233,18 @@ int sdf_join(const uint8_t* split, size_t size, uint64_t n, uint32_t E, uint32_t
     LizardGPU_planesRange_t item;
     Region src, dst, xb;
     const size_t bytes = (size_t)((last - first) * E), nr = LizardGPU_planesRangeBytes(n, E, filter, first, last, ranges, R_MAX_PIECES);
+    const hipStream_t user = dfc_user();
     size_t q;
     int rc;
-    if (!g_user) hipStreamCreateWithFlags(&g_user, hipStreamNonBlocking);
     if (!nr || region_make(&src, split, size, 1, 0x5A) || region_make(&dst, NULL, bytes, 2, 0xC3) || region_make(&xb, base, base ? bytes : 0, 3, 0x77)) return 1000;
     for (q = 0; q < nr; q++) pieces[q] = region_at(&src) + ranges[q].lo;
     memset(&item, 0, sizeof item);
     item.d_dst = region_at(&dst); item.d_base = base ? region_at(&xb) : NULL; item.nElems = n; item.first = first; item.last = last;
     item.elemSize = E; item.filter = filter; item.firstPiece = 0;
-    rc = LizardGPU_joinPlanesRange_device(1, &item, pieces, g_user);
-    hipStreamSynchronize(g_user);
+    rc = LizardGPU_joinPlanesRange_device(1, &item, pieces, user);
+    hipStreamSynchronize(user);
     if (region_fetch(&dst) || region_fetch(&src) || region_fetch(&xb)) rc = 1000;
-    else memcpy(out, dst.host + SDF_G + dst.skew, bytes);
+    else memcpy(out, region_bytes(&dst), bytes);
     region_free(&src); region_free(&dst); region_free(&xb);
     return rc;
 }
@@ -312,13 +283,13 @@ int main(void)
         f = sdf_frame(pool + n * slot, slot, 0, 3 * bs, level, 0, 1); CHECK(!LizardF_isError(f), "frame"); ADD(f);            /* refused: hi > C */
 #undef ADD
         CHECK(!sdf_run(n, frames, sizes, firstRange, nRanges, 16, ranges, 6 * bs, results, rangeAt, grown, &rc, NULL, NULL), "the batch");
-        CHECK(rc == 0 && !results[0] && !results[1] && !results[2] && !results[3], "the good frames: %d %zu %zu %zu %zu: %s", rc, results[0], results[1], results[2], results[3], g_text);
-        CHECK(results[4] == FERR(frameSize_wrong) && results[5] == FERR(frameType_unknown) && LizardGPU_frameIsError(results[6]) && results[7] == FERR(frameSize_wrong), "the refusals");
+        CHECK(rc == 0 && !results[0] && !results[1] && !results[2] && !results[3], "the good frames: %d %zu %zu %zu %zu: %s", rc, results[0], results[1], results[2], results[3], dfc_text);
+        CHECK(results[4] == LZ_FRAME_E(frameSize_wrong) && results[5] == LZ_FRAME_E(frameType_unknown) && LizardGPU_frameIsError(results[6]) && results[7] == LZ_FRAME_E(frameSize_wrong), "the refusals");
         CHECK(rangeAt[16] == 6 * bs && grown[0] == 6 && grown[1] == 4 && grown[2] == 4 && grown[3] == 1, "places and statistics: %llu bytes, %llu %llu %llu %llu",
               (unsigned long long)rangeAt[16], grown[0], grown[1], grown[2], grown[3]);
         before = sdf_launches(0);
         CHECK(!sdf_run(n, frames, sizes, firstRange, nRanges, 16, ranges, 6 * bs - 1, results, rangeAt, grown, &rc, NULL, NULL), "one byte short");
-        CHECK(rc == -LIZARDGPU_ERR_ARG && strstr(g_text, "dstMaxSize_tooSmall") && sdf_launches(0) == before, "one byte short: %d, %s", rc, g_text);
+        CHECK(rc == -LIZARDGPU_ERR_ARG && strstr(dfc_text, "dstMaxSize_tooSmall") && sdf_launches(0) == before, "one byte short: %d, %s", rc, dfc_text);
     }
     free(pool);
     printf("slice_device_fake: ok, %llu ops\n", fh_ops_run());

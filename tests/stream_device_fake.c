@@ -17,12 +17,10 @@
 #include <string.h>
 
 #include "../lizard_amd/csrc/lizard_stream_device.c"       /* unit under test, compiled into this harness */
-#include "../lizard_amd/csrc/lizard_xxhash.h"
-#include "fake_hip.h"
+#include "device_fake_common.h"
 #include "lizard_oracle.h"
 
-static int g_refusePack;
-void sdf_refuse_pack(int nth) { LzGuard g; lzk_guard_acquire(&g); g_refusePack = nth; lzk_guard_release(&g); }
+void sdf_refuse_pack(int nth) { dfc_refuse_set(0, nth); }
 
 /* ---- lz_stream_scan_kernel + lz_frames_gather_kernel: block after block, the carry advancing as the records are placed ---- */
 typedef struct { const uint8_t* base; const uint64_t* blkOffsets; const uint32_t *blkSizes, *blkFrames; const uint8_t* slots; size_t slot;
@@ -66,7 +64,7 @@ int lzk_stream_pack_launch(const void* d_base, const uint64_t* d_blkOffsets, con
     if (!d_base || !d_blkOffsets || !d_blkSizes || !d_blkFrames || !d_slots || !d_sizes || !d_offsets || !d_frames || !d_entries || !d_state || nb == 0) {
         snprintf(lzk_err(), LZK_ERR_BYTES, "lzk_stream_pack_launch: bad argument"); return -LIZARDGPU_ERR_ARG;
     }
-    if (g_refusePack && !--g_refusePack) { snprintf(lzk_err(), LZK_ERR_BYTES, "lzk_stream_pack_launch: refused by the test"); return -LIZARDGPU_ERR_HIP; }
+    if (dfc_refused(0, "lzk_stream_pack_launch")) return -LIZARDGPU_ERR_HIP;
     k.base = (const uint8_t*)d_base; k.blkOffsets = d_blkOffsets; k.blkSizes = d_blkSizes; k.blkFrames = d_blkFrames; k.slots = (const uint8_t*)d_slots;
     k.slot = slot; k.sizes = d_sizes; k.offsets = d_offsets; k.nb = nb; k.first = firstBlock; k.frames = d_frames; k.entries = d_entries; k.state = d_state;
     k.capacity = capacity;
@@ -74,27 +72,7 @@ int lzk_stream_pack_launch(const void* d_base, const uint64_t* d_blkOffsets, con
 }
 
 /* ---- lz_xxh32_frames_kernel ---- */
-typedef struct { LzFramesEntry* frames; uint32_t n; } FramesHashK;
-static void frames_hash_kernel(void* a)
-{
-    const FramesHashK* k = (const FramesHashK*)a;
-    const uint32_t want = LZK_FRAMES_LIVE | LZK_FRAMES_CHECKSUM;
-    uint32_t f;
-    if (!fh_check_dev(k->frames, (size_t)k->n * sizeof *k->frames, "frames hash: the frame table")) return;
-    for (f = 0; f < k->n; f++) {
-        LzFramesEntry* e = k->frames + f;
-        if ((e->flags & want) != want) continue;
-        if (e->srcSize && !fh_check_dev((const void*)(uintptr_t)e->src, (size_t)e->srcSize, "frames hash: a frame's source")) continue;
-        e->hash = Lizard_XXH32((const void*)(uintptr_t)e->src, (size_t)e->srcSize, 0);
-    }
-}
-int lzk_frames_hash_launch(LzFramesEntry* d_frames, uint32_t nFrames, hipStream_t stream)
-{
-    FramesHashK k;
-    if (!d_frames || nFrames == 0) { snprintf(lzk_err(), LZK_ERR_BYTES, "lzk_frames_hash_launch: bad argument"); return -LIZARDGPU_ERR_ARG; }
-    k.frames = d_frames; k.n = nFrames;
-    return fh_enqueue_kernel(stream, frames_hash_kernel, &k, sizeof k) == hipSuccess ? 0 : -LIZARDGPU_ERR_HIP;
-}
+int lzk_frames_hash_launch(LzFramesEntry* d_frames, uint32_t nFrames, hipStream_t stream) { return dfc_frames_hash_launch(d_frames, nFrames, stream); }
 
 /* ---- lz_stream_finish_kernel ---- */
 typedef struct { const LzFramesEntry* frames; const LzStreamEntry* entries; const uint8_t* blob; const LzStreamState* state; uint32_t n;
@@ -145,17 +123,13 @@ int lzk_stream_finish_launch(const LzFramesEntry* d_frames, const LzStreamEntry*
 /* ---- one call against prefix + the host twin, frame by frame ---- */
 void pf_set_chunk_bytes(size_t n);
 void pf_shutdown(void);
-#define CHECK(cond, ...) do { if (!(cond)) { fprintf(stderr, "stream_device_fake: line %d: ", __LINE__); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); return 1; } } while (0)
-#define FERR(code) ((size_t)-(long)(LIZARDGPU_FRAME_ERR_##code))
-#define SDF_G 4096
+#define CHECK(cond, ...) DFC_CHECK("stream_device_fake", cond, __VA_ARGS__)
 #define SDF_MAX 16
 #define SDF_BLOCK ((size_t)131072)
 #define SDF_DATA (12 * SDF_BLOCK)
 enum { SDF_CAP_BOUND = 0, SDF_CAP_EXACT = 1, SDF_CAP_ONE_BELOW = 2 };
-static hipStream_t g_user;
 static uint8_t* g_data;
-static char g_text[LZK_ERR_BYTES];
-const char* sdf_last_error(void) { return g_text; }            /* LizardGPU_lastError as the last call left it (the twins' calls come behind it) */
+const char* sdf_last_error(void) { return dfc_text; }            /* LizardGPU_lastError as the last call left it (the twins' calls come behind it) */
 
 /* P50 with noise across block borders, so that raw records lie between compressed ones; the block in front of 10 * SDF_BLOCK is noise */
 static const uint8_t* sdf_data(void)
@@ -215,10 +189,12 @@ int sdf_batch(size_t nf, const size_t* offs, const size_t* sizes, const size_t* 
 {
     const uint8_t* const data = sdf_data();
     LizardF_preferences_t p;
-    uint8_t *dsrc[SDF_MAX], *hsrc[SDF_MAX], *prefix[SDF_MAX], *ddst, *hdst, *expect;
+    const hipStream_t user = dfc_user();
+    Region src[SDF_MAX], dst;
+    uint8_t *prefix[SDF_MAX], *expect;
     const void *srcs[SDF_MAX], *prefixes[SDF_MAX];
     uint64_t offsets[SDF_MAX + 1], wantOffsets[SDF_MAX + 1];
-    size_t i, q, g, total = 0, bound, cap, dn, ret, failed = 777;
+    size_t i, q, g, total = 0, bound, cap, ret, failed = 777;
     unsigned long long s0[8], s1[8];
     int bad = 0, decodable = 1;
     CHECK(nf <= SDF_MAX, "too many frames");
@@ -226,7 +202,6 @@ int sdf_batch(size_t nf, const size_t* offs, const size_t* sizes, const size_t* 
     p.frameInfo.blockSizeID = (LizardF_blockSizeID_t)bsid; p.frameInfo.blockMode = (LizardF_blockMode_t)blockMode;
     p.frameInfo.contentChecksumFlag = (LizardF_contentChecksum_t)checksum; p.compressionLevel = level;
     p.frameInfo.contentSize = 1;                            /* (not zero: every frame writes its own size) */
-    if (!g_user) hipStreamCreateWithFlags(&g_user, hipStreamNonBlocking);
     bound = LizardGPU_compressStreamBound(nf, sizes, prefixSizes, &p);
     CHECK(!LizardF_isError(bound), "the bound is an error code");
     /* what the stream must be: prefix + the host twin's frame at bound + 8, when the call is to succeed or to miss its capacity */
@@ -236,7 +211,7 @@ int sdf_batch(size_t nf, const size_t* offs, const size_t* sizes, const size_t* 
         prefix[i] = (uint8_t*)malloc(pre + 1); sdf_prefix(prefix[i], pre, i); prefixes[i] = prefix[i];
         if (pre && pre < 8) decodable = 0;
         wantOffsets[i] = total;
-        if (wantFailed >= 0 || (want && want != FERR(dstMaxSize_tooSmall))) continue;
+        if (wantFailed >= 0 || (want && want != LZ_FRAME_E(dstMaxSize_tooSmall))) continue;
         memcpy(expect + total, prefix[i], pre); total += pre;
         p.frameInfo.contentSize = sizes[i];
         q = LizardGPU_compressFrame(expect + total, LizardGPU_compressFrameBound(sizes[i], &p) + 8, data + offs[i], sizes[i], &p);
@@ -246,51 +221,37 @@ int sdf_batch(size_t nf, const size_t* offs, const size_t* sizes, const size_t* 
     }
     wantOffsets[nf] = total;
     cap = capMode == SDF_CAP_BOUND ? bound : capMode == SDF_CAP_EXACT ? total : total - 1;
-    dn = cap + 2 * SDF_G;
     for (i = 0; i < nf; i++) {
-        const size_t n = sizes[i], sn = n + 2 * SDF_G + 4, skew = i % 4;
-        CHECK(offs[i] + n <= SDF_DATA, "a frame outside the data");
-        CHECK(hipMalloc((void**)&dsrc[i], sn) == hipSuccess && hipHostMalloc((void**)&hsrc[i], sn, 0) == hipSuccess, "allocation");
-        memset(hsrc[i], 0x5A, sn); if (n) memcpy(hsrc[i] + SDF_G + skew, data + offs[i], n);
-        hipMemcpyAsync(dsrc[i], hsrc[i], sn, hipMemcpyHostToDevice, g_user);
-        srcs[i] = (nullMask >> i) & 1u ? NULL : dsrc[i] + SDF_G + skew;
+        CHECK(offs[i] + sizes[i] <= SDF_DATA, "a frame outside the data");
+        CHECK(!region_make(&src[i], data + offs[i], sizes[i], i % 4, 0x5A), "allocation");
+        srcs[i] = (nullMask >> i) & 1u ? NULL : region_at(&src[i]);
     }
-    CHECK(hipMalloc((void**)&ddst, dn) == hipSuccess && hipHostMalloc((void**)&hdst, dn, 0) == hipSuccess, "allocation");
-    memset(hdst, 0xC3, dn);
-    hipMemcpyAsync(ddst, hdst, dn, hipMemcpyHostToDevice, g_user);
-    if (failMalloc) hipStreamSynchronize(g_user);          /* (a call that fails before it orders itself behind the caller's stream leaves that stream's work queued, as it may) */
+    CHECK(!region_make(&dst, NULL, cap, 0, 0xC3), "allocation");
+    if (failMalloc) hipStreamSynchronize(user);          /* (a call that fails before it orders itself behind the caller's stream leaves that stream's work queued, as it may) */
     memcpy(s0, lzk_ctx_peek()->devStreamCompressStats, 4 * sizeof s0[0]); memcpy(s0 + 4, lzk_ctx_peek()->devFrameCompressStats, 4 * sizeof s0[0]);
     for (i = 0; i <= nf; i++) offsets[i] = 0xDEADBEEFull;
     fh_fail_malloc(failMalloc);
-    ret = LizardGPU_compressStream_device(ddst + SDF_G, cap, nf, srcs, sizes, prefixSizes ? prefixes : NULL, prefixSizes, &p, offsets, &failed, g_user);
+    ret = LizardGPU_compressStream_device(region_at(&dst), cap, nf, srcs, sizes, prefixSizes ? prefixes : NULL, prefixSizes, &p, offsets, &failed, user);
     fh_fail_malloc(0);
-    snprintf(g_text, sizeof g_text, "%s", LizardGPU_lastError());
+    dfc_keep_text();
     memcpy(s1, lzk_ctx_peek()->devStreamCompressStats, 4 * sizeof s1[0]); memcpy(s1 + 4, lzk_ctx_peek()->devFrameCompressStats, 4 * sizeof s1[0]);
     for (g = 0; g < 8 && grown; g++) grown[g] = s1[g] - s0[g];
-    hipStreamSynchronize(g_user);                          /* (a call that refused up front never touched the caller's stream) */
-    memset(hdst, 0, dn);
-    hipMemcpy(hdst, ddst, dn, hipMemcpyDeviceToHost);
-    for (q = 0; q < SDF_G && !bad; q++) if (hdst[q] != 0xC3 || hdst[SDF_G + cap + q] != 0xC3) bad = 1;
-    for (i = 0; i < nf && !bad; i++) {
-        const size_t n = sizes[i], sn = n + 2 * SDF_G + 4, skew = i % 4;
-        memset(hsrc[i], 0, sn);
-        hipMemcpy(hsrc[i], dsrc[i], sn, hipMemcpyDeviceToHost);
-        for (q = 0; q < SDF_G; q++) if (hsrc[i][q] != 0x5A || hsrc[i][SDF_G + skew + n + q] != 0x5A) bad = 1;
-        if (!bad && n && memcmp(hsrc[i] + SDF_G + skew, data + offs[i], n)) bad = 1;
-    }
+    hipStreamSynchronize(user);                          /* (a call that refused up front never touched the caller's stream) */
+    if (region_fetch(&dst) && !bad) bad = 1;
+    for (i = 0; i < nf && !bad; i++) if (region_fetch_same(&src[i], data + offs[i])) bad = 1;
     if (!bad && ret != (want ? want : total)) bad = 2;
     if (!bad && wantFailed >= 0 && failed != (size_t)wantFailed) bad = 5;
-    if (!bad && wantFailed >= 0) for (q = 0; q < cap; q++) if (hdst[SDF_G + q] != 0xC3) { bad = 6; break; }
-    if (!bad && !want && memcmp(hdst + SDF_G, expect, total)) bad = 3;
+    if (!bad && wantFailed >= 0) for (q = 0; q < cap; q++) if (region_bytes(&dst)[q] != 0xC3) { bad = 6; break; }
+    if (!bad && !want && memcmp(region_bytes(&dst), expect, total)) bad = 3;
     if (!bad && !want && memcmp(offsets, wantOffsets, 8 * (nf + 1))) bad = 4;
     for (i = 0; i < nf && !bad && !want && decodable; i++)
-        if (sdf_decode(hdst + SDF_G, (size_t)offsets[i], (size_t)offsets[i + 1], data + offs[i], sizes[i])) bad = 7;
+        if (sdf_decode(region_bytes(&dst), (size_t)offsets[i], (size_t)offsets[i + 1], data + offs[i], sizes[i])) bad = 7;
     if (bad) fprintf(stderr, "stream_device_fake: %s (returned %zu, wanted %zu, total %zu; frames %zu level %d checksum %d cap %zu bound %zu failed %zu): %s\n",
                      bad == 1 ? "a canary margin or a source changed" : bad == 2 ? "unexpected return value" : bad == 3 ? "stream bytes differ from prefix + the twins' frames"
                      : bad == 4 ? "wrong frame offsets" : bad == 5 ? "wrong failed frame" : bad == 6 ? "a call refused up front wrote to d_dst"
-                     : bad == 7 ? "LizardF_decompress does not read a frame back" : "the twin refused", ret, want, total, nf, level, checksum, cap, bound, failed, g_text);
-    for (i = 0; i < nf; i++) { hipFree(dsrc[i]); hipHostFree(hsrc[i]); free(prefix[i]); }
-    hipFree(ddst); hipHostFree(hdst); free(expect);
+                     : bad == 7 ? "LizardF_decompress does not read a frame back" : "the twin refused", ret, want, total, nf, level, checksum, cap, bound, failed, dfc_text);
+    for (i = 0; i < nf; i++) { region_free(&src[i]); free(prefix[i]); }
+    region_free(&dst); free(expect);
     CHECK(!bad, "the call is wrong");
     return 0;
 }
@@ -317,16 +278,16 @@ int main(void)
         if (sdf_batch(9, offs, sizes, pre, level, 1, 1, checksum, SDF_CAP_BOUND, 0, 0, 0, -1, grown)) return 1;
         CHECK(grown[0] == 9 && grown[1] >= 2 && grown[3] == 1 && !grown[4] && !grown[5] && !grown[6], "statistics: %llu frames, %llu raw, %llu calls", grown[0], grown[1], grown[3]);
         if (sdf_batch(9, offs, sizes, NULL, level, 1, 1, !checksum, SDF_CAP_EXACT, 0, 0, 0, -1, NULL)) return 1;
-        if (sdf_batch(9, offs, sizes, pre, level, 1, 1, checksum, SDF_CAP_ONE_BELOW, 0, 0, FERR(dstMaxSize_tooSmall), -1, NULL)) return 1;
-        if (sdf_batch(9, offs, sizes, pre, 23, 1, 1, checksum, SDF_CAP_BOUND, 0, 0, FERR(compressionLevel_invalid), 0, grown)) return 1;
+        if (sdf_batch(9, offs, sizes, pre, level, 1, 1, checksum, SDF_CAP_ONE_BELOW, 0, 0, LZ_FRAME_E(dstMaxSize_tooSmall), -1, NULL)) return 1;
+        if (sdf_batch(9, offs, sizes, pre, 23, 1, 1, checksum, SDF_CAP_BOUND, 0, 0, LZ_FRAME_E(compressionLevel_invalid), 0, grown)) return 1;
         CHECK(grown[2] == 0 && grown[3] == 0, "a stream of level 23 launched something");
-        if (sdf_batch(4, lateOffs, lateSizes, pre, level, 1, 0, checksum, SDF_CAP_BOUND, 0, 0, FERR(blockMode_invalid), 2, NULL)) return 1;
-        if (sdf_batch(9, offs, sizes, pre, level, 1, 1, checksum, SDF_CAP_BOUND, 1u << 4 | 1u << 7, 0, FERR(GENERIC), 4, NULL)) return 1;
+        if (sdf_batch(4, lateOffs, lateSizes, pre, level, 1, 0, checksum, SDF_CAP_BOUND, 0, 0, LZ_FRAME_E(blockMode_invalid), 2, NULL)) return 1;
+        if (sdf_batch(9, offs, sizes, pre, level, 1, 1, checksum, SDF_CAP_BOUND, 1u << 4 | 1u << 7, 0, LZ_FRAME_E(GENERIC), 4, NULL)) return 1;
         /* a refused launch, a failing allocation (fresh stages: one of the first hipMallocs of the call); then a good call */
         sdf_refuse_pack(s & 1 ? 2 : 1);
-        if (sdf_batch(6, offs, sizes, pre, level, 1, 1, checksum, SDF_CAP_BOUND, 0, 0, FERR(GENERIC), -1, NULL)) return 1;
+        if (sdf_batch(6, offs, sizes, pre, level, 1, 1, checksum, SDF_CAP_BOUND, 0, 0, LZ_FRAME_E(GENERIC), -1, NULL)) return 1;
         pf_shutdown();
-        if (sdf_batch(6, offs, sizes, pre, level, 1, 1, checksum, SDF_CAP_BOUND, 0, 1 + (int)(s % 3), FERR(GENERIC), -1, NULL)) return 1;
+        if (sdf_batch(6, offs, sizes, pre, level, 1, 1, checksum, SDF_CAP_BOUND, 0, 1 + (int)(s % 3), LZ_FRAME_E(GENERIC), -1, NULL)) return 1;
         if (sdf_batch(6, offs, sizes, pre, level, 1, 1, checksum, SDF_CAP_BOUND, 0, 0, 0, -1, NULL)) return 1;
     }
     unsetenv("LIZARDGPU_FRAME_CHUNK_BLOCKS");

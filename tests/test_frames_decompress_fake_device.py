@@ -38,22 +38,7 @@ GOLDEN = os.path.join(util.GOLDEN_DIR, "frame_ref_linked.liz").encode()
 def built(kind):
     """'lib': the harness with the batch decoder as a shared library; 'asan': tests/unframes_device_fake.c's program under
     AddressSanitizer + UBSan.  The emulator's objects are the plain ones test_pipeline_fake builds."""
-    util.oracle()
-    objs = []
-    for src in (os.path.join(HERE, "pipeline_fake_emul.cpp"), os.path.join(HERE, "emul", "simt.cpp")):
-        obj = os.path.join(pf._dir, os.path.basename(src) + ".o")
-        if not os.path.exists(obj):
-            subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-fno-omit-frame-pointer", "-Wno-unused-function", "-Wno-unknown-pragmas",
-                                   "-pthread", "-I", os.path.join(HERE, "emul"), "-I", HERE, "-c", src, "-o", obj])
-        objs.append(obj)
-    flags = {"lib": ["-shared", "-Wl,-Bsymbolic"], "asan": ["-DUNFRAMES_DEVICE_FAKE_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]}[kind]
-    out = os.path.join(pf._dir, "libunframes_device_fake.so" if kind == "lib" else "unframes_device_fake_" + kind)
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu99", "-fPIC", "-Wall", "-Wextra", "-D__HIP_PLATFORM_AMD__", "-DLZV_HASH_PIECE=40961",
-                           "-I/opt/rocm/include", "-I" + os.path.join(util.ROOT, "include"), "-I" + util.ORACLE_DIR, "-I" + HERE] + flags
-                          + [os.path.join(HERE, "unframes_device_fake.c"), os.path.join(HERE, "pipeline_fake.c"), os.path.join(HERE, "fake_hip.c")]
-                          + [os.path.join(pf.CSRC, f) for f in ("lizard_frame_host.c", "lizard_decode_host.c", "lizard_xxhash.c")] + objs
-                          + ["-o", out, "-L" + util.ORACLE_DIR, "-llizard_oracle", "-lpthread", "-lstdc++", "-Wl,-rpath," + util.ORACLE_DIR])
-    return out
+    return util.build_fake(pf._dir, kind, "unframes_device_fake", ("unframes_device_fake.c", "pipeline_fake.c", "fake_hip.c"))
 
 
 @functools.lru_cache(maxsize=None)

@@ -44,23 +44,7 @@ def built(kind):
     """'lib': the harness as a shared library for ctypes; 'asan' / 'tsan': as a program with that sanitizer.  The emulator's objects
     are built plain in every form (its lanes switch stacks by hand, which the sanitizers' instrumentation does not follow).
     lizard_unframe_device.c (tests/test_pipeline_fake_device.py) is compiled in with a small odd piece size for its checksum pass."""
-    util.oracle()
-    objs = []
-    for src in (os.path.join(HERE, "pipeline_fake_emul.cpp"), os.path.join(HERE, "emul", "simt.cpp")):
-        obj = os.path.join(_dir, os.path.basename(src) + ".o")
-        if not os.path.exists(obj):
-            subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-fno-omit-frame-pointer", "-Wno-unused-function", "-Wno-unknown-pragmas",
-                                   "-pthread", "-I", os.path.join(HERE, "emul"), "-I", HERE, "-c", src, "-o", obj])
-        objs.append(obj)
-    flags = {"lib": ["-shared", "-Wl,-Bsymbolic"], "asan": ["-DPIPELINE_FAKE_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
-             "tsan": ["-DPIPELINE_FAKE_MAIN", "-fsanitize=thread"]}[kind]
-    out = os.path.join(_dir, "libpipeline_fake.so" if kind == "lib" else "pipeline_fake_" + kind)
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu99", "-fPIC", "-Wall", "-Wextra", "-D__HIP_PLATFORM_AMD__", "-DLZV_HASH_PIECE=40961", "-I/opt/rocm/include",
-                           "-I" + os.path.join(util.ROOT, "include"), "-I" + util.ORACLE_DIR, "-I" + HERE] + flags
-                          + [os.path.join(HERE, "pipeline_fake.c"), os.path.join(HERE, "fake_hip.c")]
-                          + [os.path.join(CSRC, f) for f in ("lizard_frame_host.c", "lizard_decode_host.c", "lizard_xxhash.c")] + objs
-                          + ["-o", out, "-L" + util.ORACLE_DIR, "-llizard_oracle", "-lpthread", "-lstdc++", "-Wl,-rpath," + util.ORACLE_DIR])
-    return out
+    return util.build_fake(_dir, kind, "pipeline_fake", ("pipeline_fake.c", "fake_hip.c"))
 
 
 @functools.lru_cache(maxsize=None)

@@ -178,18 +178,10 @@ def test_the_bound_is_the_obvious_sum():
     assert bound([(B - 1, B)], B) == B and bound([(0, 2 * B)], B) == 2 * B          # a range ending exactly on a block edge
 
 
-def sanitizer_runtime():
-    src, exe = os.path.join(_dir, "asan_probe.c"), os.path.join(_dir, "asan_probe")
-    with open(src, "w") as f:
-        f.write("int main(void) { return 0; }\n")
-    return subprocess.run(["gcc", "-fsanitize=address,undefined", src, "-o", exe], capture_output=True).returncode == 0 \
-        and subprocess.run([exe], capture_output=True).returncode == 0
-
-
 def test_the_arithmetic_as_a_stand_alone_program_under_address_sanitizer():
     """tests/planes_range_asan_main.c: every (first, last) of small buffers and the bound, every array a heap allocation of exactly
     the entries the functions may touch."""
-    if not sanitizer_runtime():
+    if not util.sanitizer_runtime(_dir):
         pytest.skip("no AddressSanitizer runtime: a trivial program does not build with -fsanitize=address,undefined")
     exe = os.path.join(_dir, "planes_range_asan_main")
     subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu99", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",

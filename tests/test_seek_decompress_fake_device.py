@@ -26,16 +26,10 @@ E_TOO_SMALL, E_BLOCK_MODE, E_TYPE, E_SIZE = 11, 3, 13, 14
 
 @functools.lru_cache(maxsize=None)
 def built():
-    """The harness as a shared library; the emulator's objects are the ones test_stream_decompress_fake_device builds."""
-    sd.built("lib")
-    objs = [os.path.join(pf._dir, os.path.basename(src) + ".o") for src in ("pipeline_fake_emul.cpp", "simt.cpp", "unstream_fake_emul.cpp")]
-    out = os.path.join(pf._dir, "libseek_device_fake.so")
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu99", "-fPIC", "-Wall", "-Wextra", "-D__HIP_PLATFORM_AMD__", "-DLZV_HASH_PIECE=40961",
-                           "-I/opt/rocm/include", "-I" + os.path.join(util.ROOT, "include"), "-I" + util.ORACLE_DIR, "-I" + HERE, "-shared", "-Wl,-Bsymbolic"]
-                          + [os.path.join(HERE, f) for f in ("seek_device_fake.c", "unstream_device_fake.c", "unframes_device_fake.c", "pipeline_fake.c", "fake_hip.c")]
-                          + [os.path.join(pf.CSRC, f) for f in ("lizard_seek_host.c", "lizard_frame_host.c", "lizard_decode_host.c", "lizard_xxhash.c")] + objs
-                          + ["-o", out, "-L" + util.ORACLE_DIR, "-llizard_oracle", "-lpthread", "-lstdc++", "-Wl,-rpath," + util.ORACLE_DIR])
-    return out
+    """The harness as a shared library; the emulator's objects are the ones in pf._dir, whichever module built them first."""
+    return util.build_fake(pf._dir, "lib", "seek_device_fake",
+                           ("seek_device_fake.c", "unstream_device_fake.c", "unframes_device_fake.c", "pipeline_fake.c", "fake_hip.c"),
+                           csrc=("lizard_seek_host.c",) + util.FAKE_CSRC, emul=util.FAKE_EMUL + ("unstream_fake_emul.cpp",))
 
 
 @functools.lru_cache(maxsize=None)

@@ -165,18 +165,10 @@ def test_every_truncation_of_a_three_item_streams_tail():
         assert read(short, len(short))[0] in (si.NONE, si.DAMAGED), cut
 
 
-def sanitizer_runtime():
-    src, exe = os.path.join(_dir, "asan_probe.c"), os.path.join(_dir, "asan_probe")
-    with open(src, "w") as f:
-        f.write("int main(void) { return 0; }\n")
-    return subprocess.run(["gcc", "-fsanitize=address,undefined", src, "-o", exe], capture_output=True).returncode == 0 \
-        and subprocess.run([exe], capture_output=True).returncode == 0
-
-
 def test_the_codec_as_a_stand_alone_program_under_address_sanitizer():
     """tests/seek_table_asan_main.c: round trips, every tail length and every single-bit change of a table, every buffer a heap
     allocation of exactly the bytes the codec may touch."""
-    if not sanitizer_runtime():
+    if not util.sanitizer_runtime(_dir):
         pytest.skip("no AddressSanitizer runtime: a trivial program does not build with -fsanitize=address,undefined")
     exe = os.path.join(_dir, "seek_table_asan_main")
     subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu99", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",

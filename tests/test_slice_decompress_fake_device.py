@@ -34,18 +34,10 @@ SCHEDULES = [s for s in pf.SCHEDULES if s[1] in (pf.LAZY, pf.RANDOM)]
 
 @functools.lru_cache(maxsize=None)
 def built(kind):
-    """'lib': the harness as a shared library; 'asan': its program under AddressSanitizer + UBSan.  The emulator's objects are the ones
-    test_frames_decompress_fake_device builds."""
-    fd.built("lib")
-    objs = [os.path.join(pf._dir, os.path.basename(src) + ".o") for src in ("pipeline_fake_emul.cpp", "simt.cpp")]
-    flags = {"lib": ["-shared", "-Wl,-Bsymbolic"], "asan": ["-DSLICE_DEVICE_FAKE_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]}[kind]
-    out = os.path.join(pf._dir, "libslice_device_fake.so" if kind == "lib" else "slice_device_fake_" + kind)
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu99", "-fPIC", "-Wall", "-Wextra", "-D__HIP_PLATFORM_AMD__", "-DLZV_HASH_PIECE=40961",
-                           "-I/opt/rocm/include", "-I" + os.path.join(util.ROOT, "include"), "-I" + util.ORACLE_DIR, "-I" + HERE] + flags
-                          + [os.path.join(HERE, f) for f in ("slice_device_fake.c", "unframes_device_fake.c", "pipeline_fake.c", "fake_hip.c")]
-                          + [os.path.join(pf.CSRC, f) for f in ("lizard_slice_host.c", "lizard_frame_host.c", "lizard_decode_host.c", "lizard_xxhash.c")] + objs
-                          + ["-o", out, "-L" + util.ORACLE_DIR, "-llizard_oracle", "-lpthread", "-lstdc++", "-Wl,-rpath," + util.ORACLE_DIR])
-    return out
+    """'lib': the harness as a shared library; 'asan': its program under AddressSanitizer + UBSan.  The emulator's objects are the ones in
+    pf._dir, whichever module built them first."""
+    return util.build_fake(pf._dir, kind, "slice_device_fake", ("slice_device_fake.c", "unframes_device_fake.c", "pipeline_fake.c", "fake_hip.c"),
+                           csrc=("lizard_slice_host.c",) + util.FAKE_CSRC)
 
 
 @functools.lru_cache(maxsize=None)

@@ -34,31 +34,8 @@ B = 131072
 def built(kind):
     """'lib': the harness as a shared library; 'asan': tests/unstream_device_fake.c's program under AddressSanitizer + UBSan.  The
     emulator's objects are the plain ones test_pipeline_fake builds."""
-    util.oracle()
-    objs = []
-    for src in (os.path.join(HERE, "pipeline_fake_emul.cpp"), os.path.join(HERE, "emul", "simt.cpp"), os.path.join(HERE, "unstream_fake_emul.cpp")):
-        obj = os.path.join(pf._dir, os.path.basename(src) + ".o")
-        if not os.path.exists(obj):
-            subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-fno-omit-frame-pointer", "-Wno-unused-function", "-Wno-unknown-pragmas",
-                                   "-pthread", "-I", os.path.join(HERE, "emul"), "-I", HERE, "-c", src, "-o", obj])
-        objs.append(obj)
-    flags = {"lib": ["-shared", "-Wl,-Bsymbolic"], "asan": ["-DUNSTREAM_DEVICE_FAKE_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]}[kind]
-    out = os.path.join(pf._dir, "libunstream_device_fake.so" if kind == "lib" else "unstream_device_fake_" + kind)
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu99", "-fPIC", "-Wall", "-Wextra", "-D__HIP_PLATFORM_AMD__", "-DLZV_HASH_PIECE=40961",
-                           "-I/opt/rocm/include", "-I" + os.path.join(util.ROOT, "include"), "-I" + util.ORACLE_DIR, "-I" + HERE] + flags
-                          + [os.path.join(HERE, f) for f in ("unstream_device_fake.c", "unframes_device_fake.c", "pipeline_fake.c", "fake_hip.c")]
-                          + [os.path.join(pf.CSRC, f) for f in ("lizard_frame_host.c", "lizard_decode_host.c", "lizard_xxhash.c")] + objs
-                          + ["-o", out, "-L" + util.ORACLE_DIR, "-llizard_oracle", "-lpthread", "-lstdc++", "-Wl,-rpath," + util.ORACLE_DIR])
-    return out
-
-
-def sanitizer_runtime():
-    """A trivial program builds and runs with -fsanitize=address,undefined: the runtime is there."""
-    src, exe = os.path.join(pf._dir, "asan_probe.c"), os.path.join(pf._dir, "asan_probe")
-    with open(src, "w") as f:
-        f.write("int main(void) { return 0; }\n")
-    return subprocess.run(["gcc", "-fsanitize=address,undefined", src, "-o", exe], capture_output=True).returncode == 0 \
-        and subprocess.run([exe], capture_output=True).returncode == 0
+    return util.build_fake(pf._dir, kind, "unstream_device_fake", ("unstream_device_fake.c", "unframes_device_fake.c", "pipeline_fake.c", "fake_hip.c"),
+                           emul=util.FAKE_EMUL + ("unstream_fake_emul.cpp",))
 
 
 @functools.lru_cache(maxsize=None)
@@ -317,7 +294,7 @@ def test_core_cases_under_address_sanitizer():
     a one-batch stream with segments of 2 and of 4 096 frames, capacities exact, one short, the first two frames and 0, truncated
     streams, a mixed stream with the reference's linked frame, garbage at the end, a refused launch of each kind and a failing
     allocation, with device allocations poisoned while host code runs."""
-    if not sanitizer_runtime():
+    if not util.sanitizer_runtime(pf._dir):
         pytest.skip("no AddressSanitizer runtime: a trivial program does not build with -fsanitize=address,undefined")
     exe = built("asan")                                     # (a failure of THIS build fails the test)
     r = subprocess.run([exe, GOLDEN], capture_output=True, text=True, timeout=600, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))

@@ -19,8 +19,7 @@
 #include <string.h>
 
 #include "../lizard_amd/csrc/lizard_unframes_device.c"     /* unit under test, compiled into this harness */
-#include "../lizard_amd/csrc/lizard_xxhash.h"
-#include "fake_hip.h"
+#include "device_fake_common.h"
 #include "lizard_oracle.h"
 
 unsigned emul_unframe_record(const void* payload, unsigned size, unsigned word, void* slot, unsigned cap, unsigned seed);      /* tests/pipeline_fake_emul.cpp */
@@ -28,14 +27,7 @@ void emul_walk_segment(const void* src, unsigned long long srcSize, unsigned lon
                        unsigned long long tableCap, unsigned long long* offs, unsigned* words, void* res, unsigned seed);
 
 enum { UDF_WALK, UDF_DECODE, UDF_SETTLE, UDF_FINISH, UDF_KINDS };
-static int g_refuse[UDF_KINDS];
-void udf_refuse(int kind, int nth) { LzGuard g; lzk_guard_acquire(&g); if (kind >= 0 && kind < UDF_KINDS) g_refuse[kind] = nth; lzk_guard_release(&g); }
-static int refused(int kind, const char* what)
-{
-    if (!g_refuse[kind] || --g_refuse[kind]) return 0;
-    snprintf(lzk_err(), LZK_ERR_BYTES, "%s: refused by the test", what);
-    return 1;
-}
+void udf_refuse(int kind, int nth) { if (kind < UDF_KINDS) dfc_refuse_set(kind, nth); }
 
 /* ---- lz_unframes_walk_kernel ---- */
 typedef struct { const LzUnframesEntry* frames; uint32_t n, want; uint64_t* offs; uint32_t* words; LzWalkResult* res; } WalkK;
@@ -60,7 +52,7 @@ int lzk_unframes_walk_launch(const LzUnframesEntry* d_frames, uint32_t nFrames, 
 {
     WalkK k;
     if (!d_frames || !d_res || nFrames == 0 || (fill && (!d_offs || !d_words))) { snprintf(lzk_err(), LZK_ERR_BYTES, "lzk_unframes_walk_launch: bad argument"); return -LIZARDGPU_ERR_ARG; }
-    if (refused(UDF_WALK, "lzk_unframes_walk_launch")) return -LIZARDGPU_ERR_HIP;
+    if (dfc_refused(UDF_WALK, "lzk_unframes_walk_launch")) return -LIZARDGPU_ERR_HIP;
     k.frames = d_frames; k.n = nFrames; k.want = fill ? LZU_DECODE : LZU_WALK; k.offs = fill ? d_offs : NULL; k.words = fill ? d_words : NULL; k.res = d_res;
     return fh_enqueue_kernel(stream, walk_kernel, &k, sizeof k) == hipSuccess ? 0 : -LIZARDGPU_ERR_HIP;
 }
@@ -74,8 +66,7 @@ static void decode_kernel(void* a)
     size_t i;
     if (!fh_check_dev(k->offs, 8 * k->n, "unframes decode: payload offsets") || !fh_check_dev(k->words, 4 * k->n, "unframes decode: words")
         || !fh_check_dev(k->recFrame, 4 * k->n, "unframes decode: the records' frames") || !fh_check_dev(k->out, 4 * k->n, "unframes decode: results")) { free(order); return; }
-    for (i = 0; i < k->n; i++) order[i] = (uint32_t)i;
-    for (i = k->n; i > 1; i--) { const size_t s = fh_rand() % i; const uint32_t t = order[i - 1]; order[i - 1] = order[s]; order[s] = t; }
+    dfc_shuffled(order, k->n);
     for (i = 0; i < k->n; i++) {
         const uint32_t b = order[i], word = k->words[b], size = word & 0x7FFFFFFFu;
         const LzUnframesEntry* e = k->frames + k->recFrame[b];
@@ -98,7 +89,7 @@ int lzk_unframes_decode_launch(LzCtx* c, const LzUnframesEntry* d_frames, const 
 {
     DecodeK k;
     if (!d_frames || !d_offs || !d_words || !d_recFrame || !d_out || nRecords == 0 || nRecords > 0xFFFFFFFFu) { snprintf(lzk_err(), LZK_ERR_BYTES, "lzk_unframes_decode_launch: bad argument"); return -LIZARDGPU_ERR_ARG; }
-    if (refused(UDF_DECODE, "lzk_unframes_decode_launch")) return -LIZARDGPU_ERR_HIP;
+    if (dfc_refused(UDF_DECODE, "lzk_unframes_decode_launch")) return -LIZARDGPU_ERR_HIP;
     k.frames = d_frames; k.offs = d_offs; k.words = d_words; k.recFrame = d_recFrame; k.out = d_out; k.n = nRecords;
     c->hostKernelMs = -1.0f;
     return fh_enqueue_kernel(stream, decode_kernel, &k, sizeof k) == hipSuccess ? 0 : -LIZARDGPU_ERR_HIP;
@@ -136,33 +127,13 @@ int lzk_unframes_settle_launch(const LzUnframesEntry* d_frames, uint32_t nFrames
 {
     SettleK k;
     if (!d_frames || !d_out || !d_results || !d_hashTab || nFrames == 0) { snprintf(lzk_err(), LZK_ERR_BYTES, "lzk_unframes_settle_launch: bad argument"); return -LIZARDGPU_ERR_ARG; }
-    if (refused(UDF_SETTLE, "lzk_unframes_settle_launch")) return -LIZARDGPU_ERR_HIP;
+    if (dfc_refused(UDF_SETTLE, "lzk_unframes_settle_launch")) return -LIZARDGPU_ERR_HIP;
     k.frames = d_frames; k.n = nFrames; k.out = d_out; k.results = d_results; k.hash = d_hashTab;
     return fh_enqueue_kernel(stream, settle_kernel, &k, sizeof k) == hipSuccess ? 0 : -LIZARDGPU_ERR_HIP;
 }
 
-/* ---- lz_xxh32_frames_kernel (as tests/frames_device_fake.c models it) ---- */
-typedef struct { LzFramesEntry* frames; uint32_t n; } HashK;
-static void hash_kernel(void* a)
-{
-    const HashK* k = (const HashK*)a;
-    const uint32_t want = LZK_FRAMES_LIVE | LZK_FRAMES_CHECKSUM;
-    uint32_t f;
-    if (!fh_check_dev(k->frames, (size_t)k->n * sizeof *k->frames, "frames hash: the frame table")) return;
-    for (f = 0; f < k->n; f++) {
-        LzFramesEntry* e = k->frames + f;
-        if ((e->flags & want) != want) continue;
-        if (e->srcSize && !fh_check_dev((const void*)(uintptr_t)e->src, (size_t)e->srcSize, "frames hash: a frame's decoded bytes")) continue;
-        e->hash = Lizard_XXH32((const void*)(uintptr_t)e->src, (size_t)e->srcSize, 0);
-    }
-}
-int lzk_frames_hash_launch(LzFramesEntry* d_frames, uint32_t nFrames, hipStream_t stream)
-{
-    HashK k;
-    if (!d_frames || nFrames == 0) { snprintf(lzk_err(), LZK_ERR_BYTES, "lzk_frames_hash_launch: bad argument"); return -LIZARDGPU_ERR_ARG; }
-    k.frames = d_frames; k.n = nFrames;
-    return fh_enqueue_kernel(stream, hash_kernel, &k, sizeof k) == hipSuccess ? 0 : -LIZARDGPU_ERR_HIP;
-}
+/* ---- lz_xxh32_frames_kernel, over the decoded frames ---- */
+int lzk_frames_hash_launch(LzFramesEntry* d_frames, uint32_t nFrames, hipStream_t stream) { return dfc_frames_hash_launch(d_frames, nFrames, stream); }
 
 /* ---- lz_unframes_finish_kernel ---- */
 typedef struct { const LzUnframesEntry* frames; uint32_t n; const LzFramesEntry* hash; LzUnframesResult* results; } FinishK;
@@ -190,48 +161,19 @@ int lzk_unframes_finish_launch(const LzUnframesEntry* d_frames, uint32_t nFrames
 {
     FinishK k;
     if (!d_frames || !d_hashTab || !d_results || nFrames == 0) { snprintf(lzk_err(), LZK_ERR_BYTES, "lzk_unframes_finish_launch: bad argument"); return -LIZARDGPU_ERR_ARG; }
-    if (refused(UDF_FINISH, "lzk_unframes_finish_launch")) return -LIZARDGPU_ERR_HIP;
+    if (dfc_refused(UDF_FINISH, "lzk_unframes_finish_launch")) return -LIZARDGPU_ERR_HIP;
     k.frames = d_frames; k.n = nFrames; k.hash = d_hashTab; k.results = d_results;
     return fh_enqueue_kernel(stream, finish_kernel, &k, sizeof k) == hipSuccess ? 0 : -LIZARDGPU_ERR_HIP;
 }
 
 /* ---- one batch against the single-frame entry, frame by frame ---- */
 void pf_shutdown(void);
-#define CHECK(cond, ...) do { if (!(cond)) { fprintf(stderr, "unframes_device_fake: line %d: ", __LINE__); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); return 1; } } while (0)
-#define FERR(code) ((size_t)-(long)(LIZARDGPU_FRAME_ERR_##code))
-#define UDF_G 4096
+#define CHECK(cond, ...) DFC_CHECK("unframes_device_fake", cond, __VA_ARGS__)
 #define UDF_MAX 16
 #define UDF_BLOCK ((size_t)131072)
 #define UDF_DATA (12 * UDF_BLOCK)
-static hipStream_t g_user;
 static uint8_t* g_data;
-static char g_text[LZK_ERR_BYTES];
-const char* udf_last_error(void) { return g_text; }            /* LizardGPU_lastError as the last batch left it (the single entry's calls come behind it) */
-
-/* a device region of n bytes from `bytes` (or of `fill`), skew bytes off the 4 KiB margin, uploaded on the caller's stream, not waited for */
-typedef struct { uint8_t *dev, *host; size_t n, skew; uint8_t fill; } Region;
-static int region_make(Region* r, const uint8_t* bytes, size_t n, size_t skew, uint8_t fill)
-{
-    const size_t all = n + 2 * UDF_G + 4;
-    r->n = n; r->skew = skew; r->fill = fill;
-    if (hipMalloc((void**)&r->dev, all) != hipSuccess || hipHostMalloc((void**)&r->host, all, 0) != hipSuccess) return 1;
-    memset(r->host, fill, all);
-    if (bytes && n) memcpy(r->host + UDF_G + skew, bytes, n);
-    return hipMemcpyAsync(r->dev, r->host, all, hipMemcpyHostToDevice, g_user) != hipSuccess;
-}
-static uint8_t* region_at(const Region* r) { return r->dev + UDF_G + r->skew; }
-/* downloads; 0 when the margins hold `fill`; the region's bytes are at host + UDF_G + skew then */
-static int region_fetch(Region* r)
-{
-    const size_t all = r->n + 2 * UDF_G + 4;
-    size_t q;
-    memset(r->host, 0, all);
-    if (hipMemcpy(r->host, r->dev, all, hipMemcpyDeviceToHost) != hipSuccess) return 1;
-    for (q = 0; q < UDF_G + r->skew; q++) if (r->host[q] != r->fill) return 1;
-    for (q = UDF_G + r->skew + r->n; q < all; q++) if (r->host[q] != r->fill) return 1;
-    return 0;
-}
-static void region_free(Region* r) { hipFree(r->dev); hipHostFree(r->host); }
+const char* udf_last_error(void) { return dfc_text; }            /* LizardGPU_lastError as the last batch left it (the single entry's calls come behind it) */
 
 /* Frame i: sizes[i] bytes at frames[i] (host memory), capacity caps[i]; nullIdx >= 0: that entry's destination is NULL.  wantRc: what
  * the call must return.  0: every results[i], consumed[i] and the decoded bytes equal LizardGPU_decompressFrame_device's for the same
@@ -245,43 +187,43 @@ int udf_batch(size_t nf, const uint8_t* const* frames, const size_t* sizes, cons
     void* dsts[UDF_MAX]; const void* srcs[UDF_MAX];
     size_t results[UDF_MAX], used[UDF_MAX], i, g;
     unsigned long long s0[4], s1[4];
+    const hipStream_t user = dfc_user();
     int rc, bad = 0;
     CHECK(nf <= UDF_MAX, "too many frames");
-    if (!g_user) hipStreamCreateWithFlags(&g_user, hipStreamNonBlocking);
     for (i = 0; i < nf; i++) {
         CHECK(!region_make(&src[i], frames[i], sizes[i], i % 4, 0x5A) && !region_make(&dst[i], NULL, caps[i], (3 * i) % 4, 0xC3), "allocation");
         srcs[i] = region_at(&src[i]); dsts[i] = (int)i == nullIdx ? NULL : region_at(&dst[i]); results[i] = 12345; used[i] = 12345;
     }
-    if (failMalloc) hipStreamSynchronize(g_user);          /* (a call that fails before it orders itself behind the caller's stream leaves that stream's work queued, as it may) */
+    if (failMalloc) hipStreamSynchronize(user);          /* (a call that fails before it orders itself behind the caller's stream leaves that stream's work queued, as it may) */
     LizardGPU_framesDecodeDeviceStats(s0);
     fh_fail_malloc(failMalloc);
-    rc = LizardGPU_decompressFrames_device(nf, dsts, caps, srcs, sizes, results, used, flags, g_user);
+    rc = LizardGPU_decompressFrames_device(nf, dsts, caps, srcs, sizes, results, used, flags, user);
     fh_fail_malloc(0);
-    snprintf(g_text, sizeof g_text, "%s", LizardGPU_lastError());
+    dfc_keep_text();
     LizardGPU_framesDecodeDeviceStats(s1);
     for (g = 0; g < 4 && grown; g++) grown[g] = s1[g] - s0[g];
-    hipStreamSynchronize(g_user);                          /* (a call that decided every frame up front never touched the caller's stream) */
+    hipStreamSynchronize(user);                          /* (a call that decided every frame up front never touched the caller's stream) */
     for (i = 0; i < nf && !bad; i++) {
         size_t t, tUsed = 777;
-        if (region_fetch(&src[i]) || region_fetch(&dst[i]) || (sizes[i] && memcmp(src[i].host + UDF_G + src[i].skew, frames[i], sizes[i]))) { bad = 1; break; }
-        if (wantRc && results[i] == FERR(GENERIC) && !used[i]) continue;      /* (a frame the failed call had not decided: nothing to compare) */
+        if (region_fetch_same(&src[i], frames[i]) || region_fetch(&dst[i])) { bad = 1; break; }
+        if (wantRc && results[i] == LZ_FRAME_E(GENERIC) && !used[i]) continue;      /* (a frame the failed call had not decided: nothing to compare) */
         CHECK(!region_make(&one, NULL, caps[i], (3 * i) % 4, 0xC3), "allocation");
-        t = LizardGPU_decompressFrame_device((int)i == nullIdx ? NULL : region_at(&one), caps[i], srcs[i], sizes[i], &tUsed, flags, g_user);
-        hipStreamSynchronize(g_user);                      /* (a call that refuses its arguments never touched the caller's stream) */
+        t = LizardGPU_decompressFrame_device((int)i == nullIdx ? NULL : region_at(&one), caps[i], srcs[i], sizes[i], &tUsed, flags, user);
+        hipStreamSynchronize(user);                      /* (a call that refuses its arguments never touched the caller's stream) */
         if (region_fetch(&one)) bad = 5;
-        if (!bad && wantRc && !(results[i] == FERR(GENERIC) || (LizardGPU_frameIsError(t) && results[i] == t) || (!t && !results[i] && used[i] == tUsed))) bad = 2;
-        if (!bad && wantRc && results[i] == FERR(GENERIC) && used[i]) bad = 2;
+        if (!bad && wantRc && !(results[i] == LZ_FRAME_E(GENERIC) || (LizardGPU_frameIsError(t) && results[i] == t) || (!t && !results[i] && used[i] == tUsed))) bad = 2;
+        if (!bad && wantRc && results[i] == LZ_FRAME_E(GENERIC) && used[i]) bad = 2;
         if (!bad && !wantRc && (results[i] != t || used[i] != tUsed)) bad = 2;
-        if (!bad && !wantRc && !LizardGPU_frameIsError(t) && t && memcmp(dst[i].host + UDF_G + dst[i].skew, one.host + UDF_G + one.skew, t)) bad = 3;
+        if (!bad && !wantRc && !LizardGPU_frameIsError(t) && t && memcmp(region_bytes(&dst[i]), region_bytes(&one), t)) bad = 3;
         region_free(&one);
         if (bad) fprintf(stderr, "unframes_device_fake: frame %zu of %zu: %s (result %zu consumed %zu, single entry %zu consumed %zu; %zu bytes, cap %zu, flags %u; call returned %d): %s\n",
                          i, nf, bad == 2 ? "unexpected result" : bad == 3 ? "decoded bytes differ from the single entry's" : "the single entry wrote outside its d_dst",
-                         results[i], used[i], t, tUsed, sizes[i], caps[i], flags, rc, g_text);
+                         results[i], used[i], t, tUsed, sizes[i], caps[i], flags, rc, dfc_text);
     }
     if (bad == 1) fprintf(stderr, "unframes_device_fake: frame %zu of %zu: a canary margin or the source changed\n", i, nf);
     for (i = 0; i < nf; i++) { region_free(&src[i]); region_free(&dst[i]); }
     CHECK(!bad, "a frame of the batch is wrong");
-    CHECK(rc == wantRc, "the call returned %d, wanted %d: %s", rc, wantRc, g_text);
+    CHECK(rc == wantRc, "the call returned %d, wanted %d: %s", rc, wantRc, dfc_text);
     return 0;
 }
 

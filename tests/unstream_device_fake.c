@@ -27,8 +27,7 @@ int LizardGPU_decompressFrames_device(size_t nFrames, void* const* d_dsts, const
                                       const size_t* srcSizes, size_t* results, size_t* srcConsumed, unsigned flags, void* stream);
 size_t LizardGPU_decompressFrame_device(void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize, size_t* srcConsumedPtr,
                                         unsigned flags, void* stream);
-#include "../lizard_amd/csrc/lizard_xxhash.h"
-#include "fake_hip.h"
+#include "device_fake_common.h"
 #include "lizard_oracle.h"
 
 void emul_unstream_segment(const void* src, unsigned long long srcSize, void* ctl, void* res, unsigned long long* offs, unsigned tableCap,
@@ -65,8 +64,7 @@ size_t usf_spy_single(void* d_dst, size_t dstCapacity, const void* d_src, size_t
 }
 
 /* ---- lz_unstream_walk_kernel ---- */
-static int g_refuse;
-void usf_refuse(int nth) { LzGuard g; lzk_guard_acquire(&g); g_refuse = nth; lzk_guard_release(&g); }      /* the n-th stream walk launch from now answers -LIZARDGPU_ERR_HIP, once */
+void usf_refuse(int nth) { dfc_refuse_set(0, nth); }      /* the n-th stream walk launch from now answers -LIZARDGPU_ERR_HIP, once */
 
 typedef struct { const uint8_t* src; uint64_t srcSize; LzStreamCtl* ctl; LzWalkResult* res; uint64_t* offs; uint32_t cap; } StreamK;
 static void stream_kernel(void* a)
@@ -80,43 +78,15 @@ int lzk_unstream_walk_launch(const void* d_src, size_t srcSize, LzStreamCtl* d_c
 {
     StreamK k;
     if (!d_src || !d_ctl || !d_res || !d_offs || tableCap == 0) { snprintf(lzk_err(), LZK_ERR_BYTES, "lzk_unstream_walk_launch: bad argument"); return -LIZARDGPU_ERR_ARG; }
-    if (g_refuse && !--g_refuse) { snprintf(lzk_err(), LZK_ERR_BYTES, "lzk_unstream_walk_launch: refused by the test"); return -LIZARDGPU_ERR_HIP; }
+    if (dfc_refused(0, "lzk_unstream_walk_launch")) return -LIZARDGPU_ERR_HIP;
     k.src = (const uint8_t*)d_src; k.srcSize = srcSize; k.ctl = d_ctl; k.res = d_res; k.offs = d_offs; k.cap = tableCap;
     return fh_enqueue_kernel(stream, stream_kernel, &k, sizeof k) == hipSuccess ? 0 : -LIZARDGPU_ERR_HIP;
 }
 
 /* ---- one stream against the loop over the single-frame entry ---- */
 void pf_shutdown(void);
-#define CHECK(cond, ...) do { if (!(cond)) { fprintf(stderr, "unstream_device_fake: line %d: ", __LINE__); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); return 1; } } while (0)
-#define FERR(code) ((size_t)-(long)(LIZARDGPU_FRAME_ERR_##code))
-#define USF_G 4096
-static hipStream_t g_user;
-static char g_text[LZK_ERR_BYTES];
-const char* usf_last_error(void) { return g_text; }           /* LizardGPU_lastError as the entry left it */
-
-/* a device region of n bytes from `bytes` (or of `fill`), skew bytes off the 4 KiB margin, uploaded on the caller's stream, not waited for */
-typedef struct { uint8_t *dev, *host; size_t n, skew; uint8_t fill; } Region;
-static int region_make(Region* r, const uint8_t* bytes, size_t n, size_t skew, uint8_t fill)
-{
-    const size_t all = n + 2 * USF_G + 8;
-    r->n = n; r->skew = skew; r->fill = fill;
-    if (hipMalloc((void**)&r->dev, all) != hipSuccess || hipHostMalloc((void**)&r->host, all, 0) != hipSuccess) return 1;
-    memset(r->host, fill, all);
-    if (bytes && n) memcpy(r->host + USF_G + skew, bytes, n);
-    return hipMemcpyAsync(r->dev, r->host, all, hipMemcpyHostToDevice, g_user) != hipSuccess;
-}
-static uint8_t* region_at(const Region* r) { return r->dev + USF_G + r->skew; }
-static int region_fetch(Region* r)                             /* downloads; 0 when the margins hold `fill` */
-{
-    const size_t all = r->n + 2 * USF_G + 8;
-    size_t q;
-    memset(r->host, 0, all);
-    if (hipMemcpy(r->host, r->dev, all, hipMemcpyDeviceToHost) != hipSuccess) return 1;
-    for (q = 0; q < USF_G + r->skew; q++) if (r->host[q] != r->fill) return 1;
-    for (q = USF_G + r->skew + r->n; q < all; q++) if (r->host[q] != r->fill) return 1;
-    return 0;
-}
-static void region_free(Region* r) { hipFree(r->dev); hipHostFree(r->host); }
+#define CHECK(cond, ...) DFC_CHECK("unstream_device_fake", cond, __VA_ARGS__)
+const char* usf_last_error(void) { return dfc_text; }           /* LizardGPU_lastError as the entry left it */
 
 /* The stream `bytes` (n of them) decoded into cap bytes.  The source starts skew bytes (0 - 7) off an aligned address.  wantGeneric 0:
  * the entry's four answers and the bytes d_dst[0 .. decoded) must be the loop's; 1: the machinery is made to fail by the caller
@@ -127,43 +97,43 @@ int usf_run(const uint8_t* bytes, size_t n, size_t cap, unsigned flags, unsigned
     Region src, dst, one;
     unsigned long long s0[4], s1[4];
     size_t r, used = 12345, frames = 12345, decoded = 12345, pos = 0, out = 0, count = 0, answer;
+    const hipStream_t user = dfc_user();
     int bad = 0, g;
-    if (!g_user) hipStreamCreateWithFlags(&g_user, hipStreamNonBlocking);
     CHECK(!region_make(&src, bytes, n, skew & 7, 0x5A) && !region_make(&dst, NULL, cap, (skew * 3) & 7, 0xC3), "allocation");
-    if (failMalloc) hipStreamSynchronize(g_user);
+    if (failMalloc) hipStreamSynchronize(user);
     g_logN = 0; g_src0 = region_at(&src); g_dst0 = region_at(&dst);
     LizardGPU_streamDecodeDeviceStats(s0);
     fh_fail_malloc(failMalloc);
-    r = LizardGPU_decompressStream_device(region_at(&dst), cap, region_at(&src), n, &used, &frames, &decoded, flags, g_user);
+    r = LizardGPU_decompressStream_device(region_at(&dst), cap, region_at(&src), n, &used, &frames, &decoded, flags, user);
     fh_fail_malloc(0);
-    snprintf(g_text, sizeof g_text, "%s", LizardGPU_lastError());
+    dfc_keep_text();
     LizardGPU_streamDecodeDeviceStats(s1);
-    hipStreamSynchronize(g_user);
+    hipStreamSynchronize(user);
     if (got) { got[0] = r; got[1] = used; got[2] = frames; got[3] = decoded; for (g = 0; g < 4; g++) got[4 + g] = s1[g] - s0[g]; }
-    if (region_fetch(&src) || region_fetch(&dst) || (n && memcmp(src.host + USF_G + src.skew, bytes, n))) bad = 1;
+    if (region_fetch_same(&src, bytes) || region_fetch(&dst)) bad = 1;
     /* the loop */
     CHECK(!region_make(&one, NULL, cap, (skew * 3) & 7, 0xC3), "allocation");
     answer = 0;
     while (!bad && pos < n) {
         size_t u = 777;
-        const size_t t = LizardGPU_decompressFrame_device(region_at(&one) + out, cap - out, region_at(&src) + pos, n - pos, &u, flags, g_user);
-        hipStreamSynchronize(g_user);
+        const size_t t = LizardGPU_decompressFrame_device(region_at(&one) + out, cap - out, region_at(&src) + pos, n - pos, &u, flags, user);
+        hipStreamSynchronize(user);
         if (LizardGPU_frameIsError(t)) { answer = t; break; }
         out += t; pos += u; count++;
     }
     if (!answer) answer = out;
-    hipStreamSynchronize(g_user);
+    hipStreamSynchronize(user);
     if (!bad && region_fetch(&one)) bad = 5;
     if (!bad && wantGeneric) {
-        if (r != FERR(GENERIC) || !g_text[0]) bad = 6;
-        else if (frames > count || decoded > out || (decoded && memcmp(dst.host + USF_G + dst.skew, one.host + USF_G + one.skew, decoded))) bad = 3;
+        if (r != LZ_FRAME_E(GENERIC) || !dfc_text[0]) bad = 6;
+        else if (frames > count || decoded > out || (decoded && memcmp(region_bytes(&dst), region_bytes(&one), decoded))) bad = 3;
     }
     if (!bad && !wantGeneric && (r != answer || used != pos || frames != count || decoded != out)) bad = 2;
-    if (!bad && !wantGeneric && out && memcmp(dst.host + USF_G + dst.skew, one.host + USF_G + one.skew, out)) bad = 3;
+    if (!bad && !wantGeneric && out && memcmp(region_bytes(&dst), region_bytes(&one), out)) bad = 3;
     if (bad) fprintf(stderr, "unstream_device_fake: %s (entry: %zu, consumed %zu, %zu frames, %zu decoded; loop: %zu, consumed %zu, %zu frames, %zu decoded; %zu bytes, cap %zu, flags %u): %s\n",
                      bad == 1 ? "a canary margin or the source changed" : bad == 2 ? "the answer differs from the loop's" : bad == 3 ? "decoded bytes differ from the loop's"
                      : bad == 5 ? "the single entry wrote outside its d_dst" : "a failure of the machinery was not answered GENERIC with a text",
-                     r, used, frames, decoded, answer, pos, count, out, n, cap, flags, g_text);
+                     r, used, frames, decoded, answer, pos, count, out, n, cap, flags, dfc_text);
     region_free(&src); region_free(&dst); region_free(&one);
     return bad;
 }
@@ -174,11 +144,10 @@ int usf_index(const uint8_t* bytes, size_t n, unsigned skew, uint64_t* offs, uin
 {
     Region src;
     int rc;
-    if (!g_user) hipStreamCreateWithFlags(&g_user, hipStreamNonBlocking);
     if (region_make(&src, bytes, n, skew & 7, 0x5A)) return 1000;
-    rc = LizardGPU_streamIndex_device(region_at(&src), n, offs, fbytes, infos, nrec, maxFrames, nFrames, streamBytes, g_user);
-    snprintf(g_text, sizeof g_text, "%s", LizardGPU_lastError());
-    hipStreamSynchronize(g_user);
+    rc = LizardGPU_streamIndex_device(region_at(&src), n, offs, fbytes, infos, nrec, maxFrames, nFrames, streamBytes, dfc_user());
+    dfc_keep_text();
+    hipStreamSynchronize(dfc_user());
     if (region_fetch(&src)) rc = 1001;
     region_free(&src);
     return rc;
@@ -245,7 +214,7 @@ int main(int argc, char** argv)
         CHECK(got[2] == (golden ? 5u : 4u) && got[6] == (golden ? 1u : 0u) && got[5] == 3u, "mixed stream: %llu frames, %llu batches, %llu handed over", got[2], got[5], got[6]);
         memcpy(st + n, "\xde\xad\xbe\xef", 4);
         if (usf_run(st, n + 4, 32 * BLK, 0, 6, 0, 0, got)) return 1;
-        CHECK(got[0] == FERR(frameHeader_incomplete) && got[1] == n, "garbage at the end");
+        CHECK(got[0] == LZ_FRAME_E(frameHeader_incomplete) && got[1] == n, "garbage at the end");
         /* the machinery fails, then a good call */
         usf_refuse(1);
         if (usf_run(st, n, 32 * BLK, 0, 0, 0, 1, NULL)) return 1;

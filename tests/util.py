@@ -327,3 +327,49 @@ def compose_frame(data, level, bsid, checksum, content_size_flag, compress_block
     if checksum:
         out += struct.pack("<I", xxhash.xxh32(data, seed=0).intdigest())
     return out
+
+
+# ---- the harnesses on the fake HIP runtime (tests/fake_hip.c, tests/device_fake_common.h) --------------
+FAKE_EMUL = ("pipeline_fake_emul.cpp", os.path.join("emul", "simt.cpp"))     # the emulator's objects every harness links
+FAKE_CSRC = ("lizard_frame_host.c", "lizard_decode_host.c", "lizard_xxhash.c")
+
+
+def fake_emul_objects(out_dir, sources=FAKE_EMUL):
+    """The emulator's objects of a harness in out_dir, built plain in every form (its lanes switch stacks by hand, which the
+    sanitizers' instrumentation does not follow) and once: a module finds what another one built there."""
+    here = os.path.join(ROOT, "tests")
+    objs = []
+    for src in sources:
+        obj = os.path.join(out_dir, os.path.basename(src) + ".o")
+        if not os.path.exists(obj):
+            subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-fno-omit-frame-pointer", "-Wno-unused-function", "-Wno-unknown-pragmas",
+                                   "-pthread", "-I", os.path.join(here, "emul"), "-I", here, "-c", os.path.join(here, src), "-o", obj])
+        objs.append(obj)
+    return objs
+
+
+def build_fake(out_dir, kind, name, sources, csrc=FAKE_CSRC, emul=FAKE_EMUL, defines=()):
+    """tests/<name>.c and the other `sources` of tests/ with the files `csrc` of lizard_amd/csrc and the emulator's objects `emul`.
+    kind 'lib': lib<name>.so for ctypes; 'asan' / 'tsan': the program <name>_<kind> (-D<NAME>_MAIN, a main of its own) with that
+    sanitizer.  The path of what was built; subprocess.CalledProcessError when the build fails."""
+    here = os.path.join(ROOT, "tests")
+    oracle()
+    main = "-D" + name.upper() + "_MAIN"
+    flags = {"lib": ["-shared", "-Wl,-Bsymbolic"], "asan": [main, "-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
+             "tsan": [main, "-fsanitize=thread"]}[kind]
+    out = os.path.join(out_dir, "lib%s.so" % name if kind == "lib" else "%s_%s" % (name, kind))
+    subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu99", "-fPIC", "-Wall", "-Wextra", "-D__HIP_PLATFORM_AMD__", "-DLZV_HASH_PIECE=40961"] + list(defines)
+                          + ["-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"), "-I" + ORACLE_DIR, "-I" + here] + flags
+                          + [os.path.join(here, f) for f in sources] + [os.path.join(ROOT, "lizard_amd", "csrc", f) for f in csrc]
+                          + fake_emul_objects(out_dir, emul)
+                          + ["-o", out, "-L" + ORACLE_DIR, "-llizard_oracle", "-lpthread", "-lstdc++", "-Wl,-rpath," + ORACLE_DIR])
+    return out
+
+
+def sanitizer_runtime(out_dir):
+    """A trivial program builds and runs with -fsanitize=address,undefined: the runtime is there."""
+    src, exe = os.path.join(out_dir, "asan_probe.c"), os.path.join(out_dir, "asan_probe")
+    with open(src, "w") as f:
+        f.write("int main(void) { return 0; }\n")
+    return subprocess.run(["gcc", "-fsanitize=address,undefined", src, "-o", exe], capture_output=True).returncode == 0 \
+        and subprocess.run([exe], capture_output=True).returncode == 0
